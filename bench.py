@@ -226,6 +226,31 @@ def timed_training(y, dist, dev, rank, world, nc, img, batch, dtype, size, steps
     return base, model, trainer, imgs, targets
 
 
+DUMP_BYTES = 64 << 20     # --dump-outputs: all arrays together
+
+
+def dump_outputs(out_dir, model, trainer):
+    """What the last timed step hands its caller, as float32 DIR/<name>.npy: the loss vector step() returns, and the
+    parameters, their gradients and the BatchNorm running statistics it leaves in the model (in parameter / buffer order).
+    An array larger than its share of DUMP_BYTES is replaced by a fixed, seeded sample of its elements (in index order)."""
+    import numpy as np
+    torch.cuda.synchronize(trainer.device)
+    params = list(model.parameters())
+    arrays = {
+        "loss": trainer.loss_out,
+        "params": torch.cat([p.detach().reshape(-1) for p in params]),
+        "grads": torch.cat([p.grad.reshape(-1) for p in params]),
+        "bn_running_stats": torch.cat([b.reshape(-1) for n, b in model.named_buffers() if ".running_" in n]),
+    }
+    cap = DUMP_BYTES // len(arrays) // 4
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        if a.size > cap:
+            a = a[np.sort(np.random.default_rng(0).choice(a.size, cap, replace=False))]
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+
+
 def roofline_bf16(model, trainer, imgs, targets, nc, img, batch, size):
     """bf16: every layer of size 's' is HBM-bound, so the roofline is bytes: algorithmic activation bytes of the
     forward convolutions (each input view read once, each output written once) / HIP-event time of those launches."""
@@ -356,7 +381,12 @@ def main():
     ap.add_argument("--collectives-at-world-1", action="store_true",
                     help="with ONE rank under torch.distributed.run: still broadcast and all-reduce the gradient buckets over RCCL")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo only to rehearse the multi-rank path with several ranks sharing one GPU)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one computed (loss, parameters, gradients, BatchNorm running "
+                         "statistics; rank 0) to DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     FORCE_COLLECTIVES[0] = bool(args.collectives_at_world_1)
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -403,6 +433,8 @@ def run(args):
 
     headline = (NC, IMG, BATCH, DTYPE, SIZE) == (1, 640, 64, "f32", "s")
     base, model, trainer, imgs, targets = timed_training(y, dist, dev, rank, world, NC, IMG, BATCH, DTYPE, SIZE, args.steps, args.warmup)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, model, trainer)      # before the roofline's extra forward passes touch the model
     result = {
         "metric": "images/sec training step, 640x640 bs=64/GPU" if headline else
                   f"images/sec training step, {IMG}x{IMG} bs={BATCH}/GPU nc={NC} {DTYPE} size {SIZE} (informational shape)",

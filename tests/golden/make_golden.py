@@ -15,6 +15,7 @@ is placed in sys.modules under that name: it stores the three argument tensors a
 "keep everything".  It performs no NMS, so no NMS result in any fixture comes from it; class-aware
 NMS stays "parity unpinned" against the reference (see oracle/yolo_oracle.py header).
 """
+import math
 import os
 import sys
 import tempfile
@@ -37,6 +38,11 @@ torch.set_num_threads(8)
 
 def npy(t):
     return t.detach().cpu().numpy()
+
+
+def exact_sum(t):
+    """Correctly rounded float64 sum of a tensor's elements: independent of summation order, so of the CPU that checks it."""
+    return math.fsum(t.detach().double().reshape(-1).tolist())
 
 
 def save(name, **arrs):
@@ -185,13 +191,13 @@ def gen_model(tag, nc, S, B, lr=1e-3):
     m = ref.YOLO(num_classes=nc, img_size=S)
     sd = m.state_dict()
     out["keys"] = np.array(list(sd.keys()))
-    out["init_sum"] = np.array([float(v.double().sum()) for v in sd.values()])
-    out["init_abs"] = np.array([float(v.double().abs().sum()) for v in sd.values()])
+    out["init_sum"] = np.array([exact_sum(v) for v in sd.values()])
+    out["init_abs"] = np.array([exact_sum(v.abs()) for v in sd.values()])
     out["numel"] = np.array([v.numel() for v in sd.values()])
     g = torch.Generator().manual_seed(123)
     x = torch.rand(B, 3, S, S, generator=g)
     targets = _targets_for(nc, B, S, 2000)
-    out["x_sum"] = np.array([float(x.double().sum())])
+    out["x_sum"] = np.array([exact_sum(x)])
     m.train()
     opt = torch.optim.Adam(m.parameters(), lr=lr)
     opt.zero_grad()

@@ -1,5 +1,7 @@
 """Pins the CPU oracle (oracle/yolo_oracle.py) against outputs of the REFERENCE itself, recorded in
 tests/golden/*.npz by tests/golden/make_golden.py.  Runs on the CPU; no GPU, no reference needed."""
+import math
+
 import numpy as np
 import pytest
 import torch
@@ -12,6 +14,11 @@ torch.set_num_threads(8)
 
 def T(a):
     return torch.from_numpy(np.array(a))
+
+
+def exact_sum(t):
+    """Correctly rounded float64 sum (math.fsum): the same bits on every CPU, whatever order a vectorised sum would take."""
+    return math.fsum(t.detach().double().reshape(-1).tolist())
 
 
 def close(a, b, rtol=1e-5, atol=1e-6):
@@ -260,14 +267,14 @@ def test_full_model_step_matches_reference(tag, nc, S):
     m = _product_state(nc, S)
     sd = m.state_dict()
     assert list(sd.keys()) == list(g["keys"])
-    close([float(v.double().sum()) for v in sd.values()], g["init_sum"], 0, 0)
-    close([float(v.double().abs().sum()) for v in sd.values()], g["init_abs"], 0, 0)
+    close([exact_sum(v) for v in sd.values()], g["init_sum"], 0, 0)
+    close([exact_sum(v.abs()) for v in sd.values()], g["init_abs"], 0, 0)
     P = {k: v.clone() for k, v in sd.items()}
     names = list(g["param_names"])
     for n in names:
         P[n].requires_grad_(True)
     x = torch.rand(2, 3, S, S, generator=torch.Generator().manual_seed(123))
-    close(float(x.double().sum()), g["x_sum"][0], 0, 0)
+    close(exact_sum(x), g["x_sum"][0], 0, 0)
     targets = orc.assign_targets(orc.synthetic_boxes(2, nc, S, 8, 2000), S, nc)
     preds = orc.forward(P, x, nc, training=True)
     tot, b, o, c = orc.loss_multiscale(preds, targets, orc.anchors_of(P), nc)

@@ -270,21 +270,24 @@ class InferenceSession:
         side.wait_stream(torch.cuda.current_stream(self.device))
         with torch.cuda.stream(side):
             for _ in range(2):
-                self._enqueue(kind)            # warm-up: kernel attributes, lazy module state
+                self._enqueue(kind, lanes=False)   # warm-up: kernel attributes, lazy module state
         torch.cuda.current_stream(self.device).wait_stream(side)
         torch.cuda.synchronize(self.device)
         graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(graph):
-            self._enqueue(kind)
+            self._enqueue(kind, lanes=False)
         self.graphs[kind] = graph
         return graph
 
-    def _enqueue(self, kind: str):
+    def _enqueue(self, kind: str, lanes: bool = True):
         """Everything a replay repeats: image load, forward list, post-process.  BatchNorm folding is NOT in here: it depends on the
-        weights only and runs (eagerly, before the replay) when the weight state changed."""
+        weights only and runs (eagerly, before the replay) when the weight state changed.  lanes=False runs the forward list in
+        list order on the one stream (no side lane; the same kernels, so the same results): the capture takes that form, because
+        replaying a graph captured across the context's side stream (fork / join events between two streams) crashed the host
+        process inside hipGraphLaunch."""
         ops, n = self.plan.fwd_ops
         self.model._load_input(self.plan, self.x if kind == "f32" else self.x_u8)
-        L.run_ops(ops, n, _stream(self.device), self.plan._ctx())
+        L.run_ops(ops, n, _stream(self.device), self.plan._ctx() if lanes else None)
         preds = [v.buf.data.view(1, v.H, v.W, 3, v.C // 3) for v in self.heads]
         self.det.candidates(preds, self.model.anchors, self.S, self.conf, letterbox_dev=self.lb)
         self.det.nms(self.iou, self.nms_mode)

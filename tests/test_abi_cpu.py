@@ -194,3 +194,22 @@ def test_replacing_a_parameter_or_buffer_bumps_the_generation():
     g2 = G.PARAM_GENERATION[0]
     torch.nn.Linear(3, 3)                      # constructing modules (first registration) does not count
     assert G.PARAM_GENERATION[0] == g2
+
+
+def test_planner_admits_winograd_only_with_a_block_geometry():
+    """yh_conv_wino_blocks has no block geometry (-1) for the 2x2 planes at batch >= 25: the planner routes those layers to
+    another family instead of planning a launch conv_wino rejects (round-4 ADVICE).  Traced and compiled on the CPU (the
+    library's sizing queries are host code); nothing is launched."""
+    from yolo_from_scratch_amd import _lib as L, graph as G, modules as Mo
+    lib, dev = L.lib(), torch.device("cpu")
+    torch.manual_seed(0)
+    m = Mo.YOLO(num_classes=1, img_size=64).train()
+    plan = G.Plan(dev, (64, 3, 64, 64), True, False, "f32")
+    m._trace(plan)
+    plan.compile(m._grad_views(dev))
+    convs = [r for r in plan.recs if isinstance(r, G.ConvRec)]
+    assert any(r.k == 3 and r.s == 1 and r.x.H == 2 for r in convs)
+    for r in convs:
+        assert r.nblk > 0, (r.x.B, r.x.H, r.x.W, r.cin, r.cout)
+        if r.wino_f or r.wino_b:
+            assert lib.yh_conv_wino_blocks(r.x.B, r.x.H, r.x.W) > 0, (r.x.B, r.x.H, r.x.W, r.cin, r.cout)

@@ -16,6 +16,8 @@ from __future__ import annotations
 
 import ctypes
 import os
+import struct
+from collections import defaultdict
 from dataclasses import dataclass, field
 from typing import Dict, List, Optional, Tuple
 
@@ -68,6 +70,19 @@ def _rup4(c: int) -> int:
 
 def _rup8(c: int) -> int:
     return (c + 7) // 8 * 8
+
+
+# op kinds of the passes whose fp32 and bf16 forms take the same arguments
+_OPS = {False: dict(pool=L.OP_MAXPOOL5_FWD, pool_bwd=L.OP_MAXPOOL5_BWD, reduce=L.OP_BN_SILU_BWD_REDUCE, apply=L.OP_BN_SILU_BWD_APPLY,
+                    colsum=L.OP_COLSUM, wgrad=L.OP_CONV_BWD_WEIGHT, narrow_w=L.OP_CONV_NARROW_BWD_WEIGHT, narrow=L.OP_CONV_NARROW,
+                    narrow_s2=L.OP_CONV_NARROW_DGRAD_S2, dgrad=L.OP_CONV_BWD_DATA),
+        True: dict(pool=L.OP_BF16_MAXPOOL5_FWD, pool_bwd=L.OP_BF16_MAXPOOL5_BWD, reduce=L.OP_BF16_BN_SILU_BWD_REDUCE,
+                   apply=L.OP_BF16_BN_SILU_BWD_APPLY, colsum=L.OP_BF16_COLSUM, wgrad=L.OP_BF16_CONV_BWD_WEIGHT,
+                   narrow_w=L.OP_BF16_CONV_NARROW_BWD_WEIGHT, narrow=L.OP_BF16_CONV_NARROW, narrow_s2=L.OP_BF16_CONV_NARROW_DGRAD_S2,
+                   dgrad=L.OP_BF16_CONV_BWD_DATA)}
+# weight-transform launches (*_MULTI: one descriptor per conv) in the order they run, with the descriptor layout of each
+_TABLES = [(L.OP_FOLD_OIHW_MULTI, "<QQQQQQQQiifi"), (L.OP_PACK_WEIGHTS_MULTI, "<QQQiiiiiiii"), (L.OP_BF16_PACK_MULTI, "<QQQiiiiiiii"),
+           (L.OP_WINO_WEIGHTS_MULTI, "<QQiiii"), (L.OP_LAT_PACK_MULTI, "<QQiiii"), (L.OP_PW_PACK_MULTI, "<QQQiiiiii")]
 
 
 class Buffer:
@@ -126,6 +141,10 @@ class View:
     def ldg(self): return self.buf.grad_C
     @property
     def M(self): return self.buf.B * self.buf.H * self.buf.W
+    @property
+    def aligned4(self) -> bool:
+        """Row stride and channel offset are multiples of 4: the view is addressable in 4-channel pieces (16 bytes fp32)."""
+        return self.buf.C % 4 == 0 and self.off % 4 == 0
     def ptr(self) -> int: return self.buf.data.data_ptr() + self.buf.data.element_size() * self.off
     def gptr(self) -> int: return self.buf.grad.data_ptr() + self.buf.grad.element_size() * self.off
     def icoef_ptr(self, row: int = 0) -> int: return self.buf.icoef.data_ptr() + 4 * (row * self.buf.icoef.shape[1] + self.off)
@@ -173,7 +192,7 @@ class ConvRec:
     narrow_b: bool = False  # stride-1 backward-data on the same kernel (flipped taps)
     narrow_w: bool = False  # weight gradient on the direct pixel-reduction kernel
     s2l_f: bool = False     # forward on the LDS-staged 3x3 stride-2 kernel (conv_s2.hip)
-    cin_k: int = 0          # bf16 plan: input channels the narrow kernels read (4 of the first layer's 8 padded ones)
+    cin_k: int = 0          # input channels the narrow kernels read (bf16 plan: 4 of the first layer's 8 padded ones)
     fwd2: bool = False      # forward fused with the sibling pointwise conv (one GEMM, N = cout1 + cout2)
     nblk: int = 0           # BatchNorm partial-sum rows written by the forward kernel
     pw_b: bool = False      # backward-data on the pointwise GEMM kernel
@@ -187,6 +206,7 @@ class ConvRec:
     dyp: int = 0            # where the BatchNorm backward writes dY: over Y in place, or (virtual) into the private tensor `y` -- the
     lddy: int = 0           # raw output in the shared buffer is still being read by the consumers' weight gradients on the side lane
     kcout_b: int = 0        # K rows of the backward-data pack (> cout: a head whose gradient rows are zero-padded; 0: cout)
+    eval_fam: str = ""      # eval plan: "wino" | "pw" | "lat" | "" (gather-GEMM) fused forward; the training flags stay False
 
 
 @dataclass
@@ -320,50 +340,129 @@ class Plan:
                         out.append(p)
         return out
 
-    # ---- kernel-family routing (fp32 training plans) ---------------------------------------------------------------------
-    def _route_f32(self, r: "ConvRec", special: bool):
-        """Which kernel family runs each pass of one convolution.  Decided for every record BEFORE anything is lowered: the fusion
-        planner (_plan_fusion) needs to know whether every reader of a tensor can apply the producer's BatchNorm + SiLU itself."""
+    # ---- kernel-family routing: decided for every record before anything is lowered ------------------------------------------
+    # A family is admitted by plan-level conditions plus the library's own query (`*_ok`, `*_blocks`); a launcher condition that no
+    # query reports is written here next to a reference to the launcher.
+    def _convs(self) -> List[ConvRec]:
+        return [r for r in self.recs if isinstance(r, ConvRec)]
+
+    def _pair_siblings(self, mult: int) -> List[ConvRec]:
+        """Sibling pointwise convs reading the same input (C3 conv1 / conv2) share one backward-data GEMM over K = Cout1 + Cout2,
+        dx written once.  `mult`: the channel multiple the pair's GEMM needs.  Returns the first of each pair."""
+        groups: Dict[tuple, List[ConvRec]] = {}
+        for r in self._convs():
+            if r.k == 1 and r.s == 1 and r.bn is not None and r.cout % mult == 0:
+                groups.setdefault((id(r.x.buf), r.x.off, r.x.C), []).append(r)
+        firsts = []
+        for grp in groups.values():
+            if len(grp) == 2 and grp[0].cout == grp[1].cout and (self.need_input_grad or grp[0].x.buf is not self.input):
+                a, b = grp
+                a.pair, b.pair, a.pair_first = b, a, True
+                firsts.append(a)
+        return firsts
+
+    @staticmethod
+    def _wino_shape(r: ConvRec) -> bool:
+        return r.k == 3 and r.s == 1 and r.cin == r.weight.shape[1] and r.x.aligned4 and r.x.H % 2 == 0 and r.x.W % 2 == 0
+
+    def _wino_lds_ok(self, r: ConvRec, K: int) -> bool:
+        """Forward (K = Cin) or backward-data (K = Cout) on the LDS-staged Winograd kernel: launch_wino_lds needs K % 16 and a block
+        geometry for (B, H, W)."""
+        return self._wino_shape(r) and K % 16 == 0 and K <= 2048 and L.lib().yh_conv_wino_blocks(r.x.B, r.x.H, r.x.W) > 0
+
+    @staticmethod
+    def _pw_fits(M: int, ld: int, K: int) -> bool:
+        return 4 * ((M - 1) * ld + K) < 1 << 31        # launch_pw_gemm (conv_pw.hip): 32-bit byte offsets into the input
+
+    def _pw_ok(self, r: ConvRec) -> bool:
+        """Pointwise GEMM forward: measured faster than the gather-GEMM except when both K and N are >= 256."""
+        return r.k == 1 and r.s == 1 and r.cin == r.weight.shape[1] and r.x.aligned4 and r.cin % 8 == 0 and \
+            not (r.cin >= 256 and r.cout >= 256) and self._pw_fits(r.x.M, r.x.ld, r.cin)
+
+    def _route_f32(self, r: ConvRec, special: bool):
+        """Which kernel family runs each pass of one convolution (fp32 training).  The fusion planner (_plan_fusion) needs it for
+        every record: whether every reader of a tensor can apply the producer's BatchNorm + SiLU itself."""
         lib = L.lib()
-        use_wino = use_pw = use_pwg = use_s2m = use_narrow = special
-        r.ldwb = _rup4(r.cin)
-        r.ldwf = _rup4(r.cout)
-        r.need_dx = self.training and (self.need_input_grad or r.x.buf is not self.input)
-        wino_ok = use_wino and r.k == 3 and r.s == 1 and r.cin == r.weight.shape[1] and r.x.H % 2 == 0 and r.x.W % 2 == 0 and r.x.ld % 4 == 0
-        r.wino_f = wino_ok and r.cin % 16 == 0 and r.cin <= 2048
-        r.wino_b = wino_ok and r.need_dx and r.cout % 16 == 0 and r.cout <= 2048
-        r.wino_w = wino_ok and r.cin % 32 == 0 and r.cout % 32 == 0 and r.x.W >= 4
-        r.pw_w = use_pw and r.k == 1 and r.s == 1 and r.cin == r.weight.shape[1]
-        # pointwise GEMM kernels: measured faster than the gather-GEMM except when both K and N are >= 256
-        pw_ok = use_pwg and r.k == 1 and r.s == 1 and r.cin == r.weight.shape[1] and r.x.ld % 4 == 0
-        r.pw_f = pw_ok and r.cin % 8 == 0 and not (r.cin >= 256 and r.cout >= 256)
-        r.s2m_b = use_s2m and r.k == 3 and r.s == 2 and r.need_dx and r.cin <= 16 and r.x.ld == r.cin and r.x.W % 2 == 0 \
-            and r.cin == r.weight.shape[1]
-        # narrow high-resolution 3x3 layers: direct kernel (LDS halo patch, filter in registers, 16-wide MFMA tiles)
-        nar_ok = use_narrow and r.k == 3 and r.cin == r.weight.shape[1] and r.x.ld % 4 == 0 and r.x.off % 4 == 0
-        r.narrow_f = bool(nar_ok and lib.yh_conv_narrow_ok(r.cin, r.cout, 3, r.s))
-        if use_narrow and r.k == 3 and r.s == 2 and r.cin == 4 and r.x.ld == 4 and r.cout == 16 and r.ldwf == 16 \
-                and lib.yh_conv_narrow_ok(r.cin, r.cout, 3, r.s):
-            r.narrow_f = True                     # first layer: the same direct MFMA kernel with CIN = 4 (padded) channels
-        r.s2l_f = bool(special and not r.narrow_f and r.k == 3 and r.s == 2 and r.cin == r.weight.shape[1] and r.x.ld % 4 == 0 and
-                       r.x.off % 4 == 0 and lib.yh_conv_s2_ok(r.x.B, r.x.H, r.x.W, r.cin, r.cout))
-        r.narrow_b = bool(nar_ok and r.s == 1 and r.need_dx and lib.yh_conv_narrow_ok(r.cout, r.cin, 3, 1))
+        r.ldwb, r.ldwf, r.cin_k = _rup4(r.cin), _rup4(r.cout), r.cin
+        r.need_dx = self.need_input_grad or r.x.buf is not self.input
+        unpadded = r.cin == r.weight.shape[1]
+        r.wino_f = special and self._wino_lds_ok(r, r.cin)
+        r.wino_b = special and r.need_dx and self._wino_lds_ok(r, r.cout)
+        r.wino_w = special and self._wino_shape(r) and r.cin % 32 == 0 and r.cout % 32 == 0 and r.x.W >= 4
+        r.pw_w = special and r.k == 1 and r.s == 1 and unpadded
+        r.pw_f = special and self._pw_ok(r)
+        r.s2m_b = special and r.k == 3 and r.s == 2 and r.need_dx and r.cin <= 16 and r.x.ld == r.cin and r.x.W % 2 == 0 and unpadded
+        # narrow high-resolution 3x3 layers: direct kernel (LDS halo patch, filter in registers, 16-wide MFMA tiles); the first
+        # layer runs it with CIN = 4 (3 channels padded)
+        nar = special and r.k == 3 and unpadded and r.x.aligned4
+        r.narrow_f = bool(special and r.k == 3 and r.x.aligned4 and (unpadded or r.x.ld == r.cin == 4)
+                          and lib.yh_conv_narrow_ok(r.cin, r.cout, 3, r.s))
+        r.s2l_f = bool(special and not r.narrow_f and r.k == 3 and r.s == 2 and unpadded and r.x.aligned4 and
+                       lib.yh_conv_s2_ok(r.x.B, r.x.H, r.x.W, r.cin, r.cout))
+        r.narrow_b = bool(nar and r.s == 1 and r.need_dx and lib.yh_conv_narrow_ok(r.cout, r.cin, 3, 1))
         if r.narrow_f:
             r.wino_f = False
         if r.narrow_b:
             r.wino_b = False
-        if nar_ok and r.s == 2 and r.need_dx and lib.yh_conv_narrow_dgrad_s2_ok(r.cin, r.cout):
+        if nar and r.s == 2 and r.need_dx and lib.yh_conv_narrow_dgrad_s2_ok(r.cin, r.cout):
             r.narrow_b, r.s2m_b = True, False      # the stride-2 form of the direct backward-data kernel
-        r.narrow_w = bool(use_narrow and r.k == 3 and r.x.ld % 4 == 0
-                          and r.x.off % 4 == 0 and lib.yh_conv_narrow_bwd_weight_ok(r.cin, r.weight.shape[1], r.cout, 3, r.s))
+        r.narrow_w = bool(special and r.k == 3 and r.x.aligned4 and lib.yh_conv_narrow_bwd_weight_ok(r.cin, r.weight.shape[1], r.cout, 3, r.s))
         if r.narrow_w:
             r.wino_w = False
+        # backward-data on the pointwise GEMM: N = Cin, K = Cout (+ the sibling's Cout), dY rows of Cout (the first's) channels
+        pw_in = special and r.k == 1 and r.s == 1 and unpadded and r.x.aligned4 and r.need_dx
+        lddy = r.cout if r.bn is not None else r.out.ldg
         if r.pair is None:
-            r.pw_b = pw_ok and r.need_dx and r.cout % 8 == 0 and not (r.cout >= 256 and r.cin >= 256)
+            r.pw_b = pw_in and r.cout % 8 == 0 and not (r.cout >= 256 and r.cin >= 256) and self._pw_fits(r.x.M, lddy, r.cout)
         elif r.pair_first:
             kpair = r.cout + r.pair.cout
-            r.pw_b = r.pair.pw_b = pw_ok and r.need_dx and r.cout % 8 == 0 and r.pair.cout % 8 == 0 and \
-                not (kpair >= 256 and r.cin >= 256)
+            r.pw_b = r.pair.pw_b = pw_in and r.cout % 8 == 0 and r.pair.cout % 8 == 0 and not (kpair >= 256 and r.cin >= 256) \
+                and self._pw_fits(r.x.M, r.cout, kpair)
+
+    def _route_bf16(self, r: ConvRec):
+        """bf16 training: the bf16 gather-GEMM family (yh_bf16_conv_fwd / _bwd_data / _bwd_weight: bf16 operands, fp32 accumulation)
+        for every pass, except the narrow direct kernels of the fp32 path with bf16 storage (conv_narrow.hip) where they measured
+        faster.  cin_k = channels the narrow kernels read (4 of the first layer's 8 padded ones)."""
+        lib = L.lib()
+        cin_real = r.weight.shape[1]
+        r.need_dx = self.need_input_grad or r.x.buf is not self.input
+        r.ldwf, r.ldwb = _rup8(r.cout), _rup8(r.cin)
+        r.cin_k = 4 if (cin_real <= 4 and r.cin == 8) else r.cin
+        if r.bn is None:        # head: the loss writes a bf16 gradient zero-padded to a multiple of 8 channels
+            r.kcout_b = _rup8(r.cout)
+            if r.out.off != 0 or r.out.ldg != r.kcout_b:
+                raise NotImplementedError("head gradient must own its (padded) buffer")
+        # measured at batch 64 (tools/layer_bench.py --dtype bf16, ms narrow / generic bf16): first layer forward 0.250 / 0.358 and
+        # weight gradient 0.220 / 0.541; stem[3] forward 0.250 / 0.114, backward-data 0.295 / 0.338, weight gradient 0.274 / 0.155;
+        # 16 -> 16 forward 0.098 / 0.098, backward-data 0.114 / 0.099, weight gradient 0.113 / 0.129 per layer (8-byte pieces: twice
+        # the load instructions per byte of the fp32 form -- these kernels are bound by instruction issue and latency, not by
+        # bytes).  Each pass takes the faster kernel.  Round 3: stem[3] forward (16 -> 32, stride 2) has a bf16-MFMA form of the
+        # narrow kernel (0.112 -> 0.075 ms).
+        nar = r.k == 3 and r.bn is not None and r.x.aligned4
+        stem3 = r.s == 2 and r.cin == 16 and r.cout == 32 and r.cin == cin_real
+        r.narrow_f = bool(nar and (r.cin_k == 4 or stem3) and lib.yh_conv_narrow_ok(r.cin_k, r.cout, 3, r.s))
+        r.narrow_w = bool(nar and (r.cin_k == 4 or r.s == 1) and
+                          lib.yh_conv_narrow_bwd_weight_ok(r.cin_k, min(cin_real, r.cin_k), r.cout, 3, r.s))
+        r.narrow_b = bool(nar and r.need_dx and r.pair is None and r.cin == cin_real and r.s == 2 and
+                          lib.yh_conv_narrow_dgrad_s2_ok(r.cin, r.cout))
+
+    def _route_eval(self, r: ConvRec):
+        """Eval: one fused kernel per conv -- conv + folded-BN bias + SiLU (+residual) (+x2 upsample).  Winograd / pointwise GEMM for
+        layers with enough workgroups to fill the chip (eval_epoch, predict_batch), the latency kernel (conv_lat.hip: K split over the
+        waves of a workgroup, no split-K slabs / fences) for the small-M layers of batch-1 inference, the gather-GEMM with in-launch
+        split-K otherwise.  Recorded in eval_fam; the training flags stay False."""
+        r.ldwb, r.ldwf = _rup4(r.cin), _rup4(r.cout)
+        fast = os.environ.get("YH_EVAL_FAST", "1") != "0"
+        M = r.x.B * r.Ho * r.Wo
+        # lat: measured at batch 1, 640x640, end to end / device ms with the uint8 image: off 1.283 / 1.227, M <= 8192 0.955 / 0.842,
+        # M <= 32768 0.954 / 0.845, every layer 0.924 / 0.842 -- the 160x160 layers are a wash, larger M belongs to the throughput kernels
+        if fast and self._wino_lds_ok(r, r.cin) and ((M // 4 + 31) // 32) * ((r.cout + 63) // 64) >= 192:
+            r.eval_fam = "wino"
+        elif fast and self._pw_ok(r) and ((M + 127) // 128) * ((r.cout + 127) // 128) >= 128:
+            r.eval_fam = "pw"
+        elif fast and M <= 32768 and r.cin == r.weight.shape[1] and r.x.aligned4 and \
+                L.lib().yh_conv_lat_ok(r.x.B, r.x.H, r.x.W, r.cin, r.cout, r.k, r.s):
+            r.eval_fam = "lat"
 
     def _plan_fusion(self, special: bool):
         """Decide which Conv+BN+SiLU outputs are never materialised ("virtual"): the convolution writes its RAW output straight
@@ -371,7 +470,7 @@ class Plan:
         prologue table, and every reader -- forward kernel, weight-gradient kernel, residual add -- applies scale, shift and SiLU
         while it stages its operand (train.py:253-265 executed at the consumer).  Saves the whole bn_silu_fwd round trip (8 bytes
         per element fp32).  A tensor stays materialised when it carries a residual or an upsample, is a plan output, feeds a
-        max-pool, or has a reader whose kernel family has no prologue."""
+        max-pool, or has a reader whose kernel family has no prologue.  fp32 training plans only."""
         readers: Dict[int, List[tuple]] = {}
         for r in self.recs:
             if isinstance(r, ConvRec):
@@ -389,7 +488,7 @@ class Plan:
             if not isinstance(r, ConvRec) or r.bn is None:
                 continue
             v = r.out
-            ok = enabled and self.training and not self.bf16 and not r.upsample and r.residual is None and v.off % 4 == 0 and v.C % 4 == 0
+            ok = enabled and not r.upsample and r.residual is None and v.off % 4 == 0 and v.C % 4 == 0
             ok = ok and not any(b == id(v.buf) and overlap(v.off, v.C, o, c) for b, o, c in outs)
             n_read = 0
             for off, C, kind, c in readers.get(id(v.buf), []):
@@ -412,7 +511,7 @@ class Plan:
     def _fwd_prologue_ok(self, c: "ConvRec") -> bool:
         """Forward kernel families that can apply the producer's BatchNorm + SiLU while staging their input."""
         lib = L.lib()
-        if c.x.off % 4 or c.x.ld % 4 or c.cin % 4 or c.cin != c.weight.shape[1]:
+        if not c.x.aligned4 or c.cin % 4 or c.cin != c.weight.shape[1]:
             return False
         M = c.x.B * c.Ho * c.Wo
         if c.narrow_f:
@@ -427,7 +526,7 @@ class Plan:
 
     def _wgrad_prologue_ok(self, c: "ConvRec") -> bool:
         lib = L.lib()
-        if c.x.off % 4 or c.x.ld % 4 or c.cin % 4 or c.cin != c.weight.shape[1]:
+        if not c.x.aligned4 or c.cin % 4 or c.cin != c.weight.shape[1]:
             return False
         if c.narrow_w:
             return c.cin == 16
@@ -440,476 +539,290 @@ class Plan:
         return v is not None and any(isinstance(q, ConvRec) and q.virtual and q.out.buf is v.buf and
                                      q.out.off < v.off + v.C and v.off < q.out.off + q.out.C for q in self.recs)
 
+    # ---- lowering -----------------------------------------------------------------------------------------------------------
     def compile(self, grad_of: Optional[Dict[int, torch.Tensor]] = None):
         """Allocate per-layer scratch and emit the op lists.  grad_of maps id(param) -> tensor that
         receives its gradient (views of a flat buffer); required when training."""
-        lib = L.lib()
-        dev = self.device
-        if self.bf16:
-            return self._compile_bf16(grad_of)
-        f32 = dict(device=dev, dtype=torch.float32)
-        fwd: List[L.YhOp] = []
-        keep: List[torch.Tensor] = []          # tensors referenced only through raw pointers
-        packs: List[tuple] = []                # one descriptor per conv for the single pack launch
-        folds: List[tuple] = []                # inference: BN folded into the packed weights
-        winos: List[tuple] = []                # Winograd weight transforms (forward and backward-data)
-        latpacks: List[tuple] = []             # k-quad packs of the latency-oriented inference kernel (conv_lat.hip)
+        self._keep: List[torch.Tensor] = []       # tensors referenced only through raw pointers
+        self._grad_of = grad_of
+        if not self.training:
+            self._compile_eval()
+        elif self.bf16:
+            self._compile_bf16(grad_of)
+        else:
+            self._compile_f32(grad_of)
+        self.param_ptrs = self._signature()
+
+    def _compile_eval(self):
+        for r in self._convs():
+            self._route_eval(r)
+        rows: Dict[int, list] = defaultdict(list)
+        self.fwd_ops = _pack(self._lower_forward(self._lower_conv_eval, rows))
+        # BatchNorm folding + the transforms of the folded weights read only parameters and running statistics: they run once per
+        # weight state (refresh_folded_weights), not once per forward -- at batch 1 the fold was the longest launch of the pass
+        self.prep_ops = _pack(self._tables(rows))
+
+    def _compile_f32(self, grad_of):
         # YH_GENERIC=1: every convolution on the generic gather-GEMM / wgrad kernels instead of the specialised families
         # (Winograd, pointwise, narrow, merged stride-2): the two are independent product paths that must agree
         # (tests/test_gpu_model.py::test_full_size_step_properties); the only planner switch besides YH_EVAL_FAST
-        special = self.training and os.environ.get("YH_GENERIC", "0") != "1"
-        use_wino = use_pw = use_pwg = use_s2m = use_narrow = special
-        s2m_packs: List[L.YhOp] = []
-        pwpacks: List[tuple] = []              # k-quad interleaved weights of the pointwise GEMM kernels
-        if self.training:
-            # sibling pointwise convs (C3 conv1 / conv2) share one backward-data GEMM: K = Cout1 + Cout2
-            groups: Dict[tuple, List[ConvRec]] = {}
-            for r in self.recs:
-                if isinstance(r, ConvRec) and r.k == 1 and r.s == 1 and r.bn is not None and r.cout % 4 == 0:
-                    groups.setdefault((id(r.x.buf), r.x.off, r.x.C), []).append(r)
-            for grp in groups.values():
-                if len(grp) == 2 and grp[0].cout == grp[1].cout and (self.need_input_grad or grp[0].x.buf is not self.input):
-                    grp[0].pair, grp[1].pair = grp[1], grp[0]
-                    grp[0].pair_first = True
-                    a = grp[0]           # forward fusion (one GEMM, N = cout1 + cout2): decided here so the lowering below
-                    a.fwd2 = grp[1].fwd2 = (  # can order the fused launch before a side-lane fork
-                        use_pwg and a.cin == a.weight.shape[1] and a.x.ld % 4 == 0 and a.cin % 8 == 0
-                        and not (a.cin >= 256 and a.cout >= 256))
-        if self.training:
-            for r in self.recs:
-                if isinstance(r, ConvRec):
-                    self._route_f32(r, special)
-            self._plan_fusion(special)
-        deferred_fork = False
+        special = os.environ.get("YH_GENERIC", "0") != "1"
+        firsts = self._pair_siblings(4)
+        for r in self._convs():
+            self._route_f32(r, special)
+        for a in firsts:        # forward fusion of the siblings: one pointwise GEMM, N = cout1 + cout2
+            a.fwd2 = a.pair.fwd2 = a.pw_f
+        self._plan_fusion(special)
+        rows: Dict[int, list] = defaultdict(list)
+        fwd = self._lower_forward(self._lower_conv_f32, rows)
+        self.fwd_ops = _pack(self._tables(rows) + rows[L.OP_PACK_WEIGHTS_S2M][::-1] + fwd)
+        self.bwd_ops = _pack(self._lower_backward(grad_of))
+
+    def _compile_bf16(self, grad_of):
+        self._pair_siblings(8)
+        for r in self._convs():
+            self._route_bf16(r)
+        rows: Dict[int, list] = defaultdict(list)
+        fwd = self._lower_forward(self._lower_conv_bf16, rows)
+        self.fwd_ops = _pack(self._tables(rows) + fwd)
+        self.bwd_ops = _pack(self._lower_backward(grad_of))
+
+    def _tables(self, rows: Dict[int, list]) -> List[L.YhOp]:
+        """The weight transforms: each non-empty descriptor table packed into device memory, one *_MULTI launch per table."""
+        ops = []
+        for kind, fmt in _TABLES:
+            if rows[kind]:
+                t = torch.frombuffer(bytearray(b"".join(struct.pack(fmt, *d) for d in rows[kind])), dtype=torch.uint8).to(self.device)
+                self._keep.append(t)
+                ops.append(_op(kind, p=[t], i=[len(rows[kind])]))
+        return ops
+
+    def _lower_forward(self, lower_conv, rows: Dict[int, list]) -> List[L.YhOp]:
+        """Records in trace order: fork / join markers, pools, and `lower_conv(ri, rec, fwd, rows)` for each convolution."""
+        fwd: List[L.YhOp] = []
         for ri, r in enumerate(self.recs):
             if isinstance(r, SyncRec):
-                nxt = self.recs[ri + 1] if ri + 1 < len(self.recs) else None
-                if r.kind == "fork" and isinstance(nxt, ConvRec) and nxt.fwd2 and nxt.pair_first and nxt.lane == 1:
-                    deferred_fork = True     # the fused sibling conv runs on the main lane; fork right after it (below)
-                else:
-                    fwd.append(_op(L.OP_FORK if r.kind == "fork" else L.OP_JOIN))
-                continue
-            ln = r.lane
-            if isinstance(r, ConvRec):
-                kk = r.k * r.k
-                fused_second = r.fwd2 and r.pair is not None and not r.pair_first and r.wf is not None   # shares its sibling's matrix
-                if not self.training:
-                    r.ldwb = _rup4(r.cin)
-                if not fused_second:
-                    r.ldwf = _rup4(r.cout)
-                    r.wf = torch.empty(kk * r.cin * r.ldwf, **f32)
-                if not self.training:
-                    # eval: one fused kernel per conv -- conv + folded-BN bias + SiLU (+residual) (+x2 upsample).  BatchNorm
-                    # is folded into an OIHW copy of the weights (yh_fold_oihw_multi), which then goes through the weight
-                    # transform of whichever kernel family runs the layer: Winograd / pointwise GEMM for layers with enough
-                    # workgroups to fill the chip (eval_epoch, predict_batch), the gather-GEMM with in-launch split-K for
-                    # the small-M layers of batch-1 inference.
-                    bn = r.bn
-                    cin_real = r.weight.shape[1]
-                    fbias = torch.empty(r.cout, **f32)
-                    wfold = torch.empty(r.cout * cin_real * kk, **f32)
-                    keep += [fbias, wfold]
-                    folds.append((r.weight.data_ptr(), r.bias.data_ptr() if r.bias is not None else 0,
-                                  bn.weight.data_ptr() if bn is not None else 0, bn.bias.data_ptr() if bn is not None else 0,
-                                  bn.running_mean.data_ptr() if bn is not None else 0,
-                                  bn.running_var.data_ptr() if bn is not None else 0, wfold.data_ptr(), fbias.data_ptr(),
-                                  r.cout, cin_real * kk, float(bn.eps) if bn is not None else 0.0, 0))
-                    fast = os.environ.get("YH_EVAL_FAST", "1") != "0"
-                    M = r.x.B * r.Ho * r.Wo
-                    aligned = r.cin == cin_real and r.x.ld % 4 == 0
-                    wino_e = fast and aligned and r.k == 3 and r.s == 1 and r.x.H % 2 == 0 and r.x.W % 2 == 0 and r.cin % 16 == 0 \
-                        and r.cin <= 2048 and ((M // 4 + 31) // 32) * ((r.cout + 63) // 64) >= 192
-                    pw_e = fast and aligned and r.k == 1 and r.s == 1 and r.cin % 8 == 0 and not (r.cin >= 256 and r.cout >= 256) \
-                        and ((M + 127) // 128) * ((r.cout + 127) // 128) >= 128
-                    args = dict(i=[r.x.ld, r.ldwf, r.residual.ld if r.residual else 0, r.out.ld, r.x.B, r.x.H, r.x.W,
-                                   r.cin, r.cout, r.k, r.s, int(bn is not None), int(r.upsample)], lane=ln)
-                    # layers with few pixels (batch-1 inference): K split over the waves of a workgroup, no split-K slabs / fences
-                    # (measured at batch 1, 640x640, end to end / device ms with the uint8 image: off 1.283 / 1.227, M <= 8192 0.955 / 0.842,
-                    # M <= 32768 0.954 / 0.845, every layer 0.924 / 0.842 -- the 160x160 layers are a wash, larger M belongs to the
-                    # throughput kernels)
-                    lat_max = 32768
-                    lat_e = fast and aligned and not wino_e and not pw_e and M <= lat_max and r.cin % 8 == 0 \
-                        and bool(lib.yh_conv_lat_ok(r.x.B, r.x.H, r.x.W, r.cin, r.cout, r.k, r.s))
-                    if lat_e:
-                        r.wf = torch.zeros(kk * r.cin * r.ldwf, **f32)
-                        latpacks.append((wfold.data_ptr(), r.wf.data_ptr(), r.cout, cin_real, kk, r.ldwf))
-                        fwd.append(_op(L.OP_CONV_LAT_FWD_FUSED,
-                                       p=[r.x.ptr(), r.wf, fbias, r.residual.ptr() if r.residual else None, r.out.ptr()], **args))
-                    elif wino_e:
-                        r.wf = torch.empty(16 * r.cin * r.ldwf, **f32)
-                        winos.append((wfold.data_ptr(), r.wf.data_ptr(), r.cout, cin_real, r.ldwf, 0))
-                        fwd.append(_op(L.OP_CONV_WINO_FWD_FUSED,
-                                       p=[r.x.ptr(), r.wf, fbias, r.residual.ptr() if r.residual else None, r.out.ptr()], **args))
-                    elif pw_e:
-                        r.wf = torch.zeros(r.cin * r.ldwf, **f32)
-                        pwpacks.append((wfold.data_ptr(), r.wf.data_ptr(), 0, r.cout, r.cin, r.ldwf, r.ldwb, 0, 0))
-                        fwd.append(_op(L.OP_CONV_PW_FWD_FUSED,
-                                       p=[r.x.ptr(), r.wf, fbias, r.residual.ptr() if r.residual else None, r.out.ptr()], **args))
-                    else:
-                        packs.append((wfold.data_ptr(), r.wf.data_ptr(), 0, r.cout, cin_real, kk, r.cin, r.ldwf, r.ldwb))
-                        nws = int(lib.yh_conv_fwd_fused_ws(r.x.B, r.x.H, r.x.W, r.cin, r.cout, r.k, r.s))
-                        sws = torch.zeros(nws, **f32) if nws > 0 else None   # per layer (two lanes may run split layers at once); zero tickets
-                        if sws is not None:
-                            keep.append(sws)
-                        fwd.append(_op(L.OP_CONV_FWD_FUSED,
-                                       p=[r.x.ptr(), r.wf, fbias, r.residual.ptr() if r.residual else None, r.out.ptr(), sws],
-                                       l=[nws], **args))
-                    continue
-                if r.pair is not None and r.need_dx:
-                    if r.pair_first:      # stacked backward packs: rows [0, c1) this conv, [c1, c1 + c2) its sibling
-                        stacked = torch.empty((r.cout + r.pair.cout) * r.ldwb, **f32)
-                        if r.pw_b:        # one k-quad interleaved matrix for both: each record writes its own K rows
-                            r.wb = r.pair.wb = stacked
-                        else:
-                            r.wb, r.pair.wb = stacked[: r.cout * r.ldwb], stacked[r.cout * r.ldwb:]
-                        keep.append(stacked)
-                elif r.s2m_b:
-                    r.ldwb = _rup4(2 * r.cin)
-                    r.wb = torch.empty(6 * r.cout * r.ldwb, **f32)
-                    s2m_packs.append(_op(L.OP_PACK_WEIGHTS_S2M, p=[r.weight, r.wb], i=[r.cout, r.cin, r.ldwb]))
-                else:
-                    # K rows of the backward pack: a 1x1 head reads dY rows zero-padded to a multiple of 4 channels against zero rows here
-                    r.kcout_b = _rup4(r.cout) if (r.bn is None and r.k == 1 and not (r.wino_b or r.pw_b) and r.out.ldg >= _rup4(r.cout)) else r.cout
-                    r.wb = (torch.zeros if r.kcout_b != r.cout else torch.empty)((16 if r.wino_b else kk) * r.kcout_b * r.ldwb, **f32) \
-                        if r.need_dx else None
-                second = r.pair is not None and not r.pair_first
-                assert not r.fwd2 or r.pw_f                  # same eligibility rule (decided at pair detection)
-                if r.pw_f:                                   # the pointwise pack writes only the conv's own columns
-                    if r.fwd2 and not second:
-                        r.ldwf = r.pair.ldwf = _rup4(r.cout + r.pair.cout)
-                        r.wf = r.pair.wf = torch.zeros(r.cin * r.ldwf, **f32)
-                    elif not r.fwd2:
-                        r.wf = torch.zeros(r.cin * r.ldwf, **f32)
-                if r.pw_f or r.pw_b:
-                    koff = r.pair.cout if second else 0
-                    pwpacks.append((r.weight.data_ptr(), r.wf.data_ptr() if r.pw_f else 0, r.wb.data_ptr() if r.pw_b else 0,
-                                    r.cout, r.cin, r.ldwf, r.ldwb, koff, r.pair.cout if (second and r.fwd2) else 0))
-                if r.wino_f:
-                    r.wf = torch.empty(16 * r.cin * r.ldwf, **f32)
-                    winos.append((r.weight.data_ptr(), r.wf.data_ptr(), r.cout, r.weight.shape[1], r.ldwf, 0))
-                if r.wino_b:
-                    winos.append((r.weight.data_ptr(), r.wb.data_ptr(), r.cout, r.weight.shape[1], r.ldwb, 1))
-                if r.s2l_f:
-                    r.wf = torch.zeros(kk * r.cin * r.ldwf, **f32)
-                    latpacks.append((r.weight.data_ptr(), r.wf.data_ptr(), r.cout, r.weight.shape[1], kk, r.ldwf))
-                gen_f = not (r.wino_f or r.pw_f or r.s2l_f)            # layouts the generic pack kernel still has to write
-                gen_b = r.wb is not None and not (r.wino_b or r.pw_b or r.s2m_b)
-                if gen_f or gen_b:
-                    packs.append((r.weight.data_ptr(), r.wf.data_ptr() if gen_f else 0, r.wb.data_ptr() if gen_b else 0,
-                                  r.cout, r.weight.shape[1], kk, r.cin, r.ldwf, r.ldwb))
-                M = r.x.B * r.Ho * r.Wo
-
-                def alloc_out(c: ConvRec, nblk: int):        # raw conv output, BN coefficients and partial-sum scratch
-                    c.nblk = nblk
-                    if c.bn is not None and c.coef is None:
-                        c.y = torch.empty(c.x.B, c.Ho, c.Wo, c.cout, **f32)
-                        c.dyp, c.lddy = c.y.data_ptr(), c.cout
-                        if c.virtual:                         # the raw output lives in the output view itself (never normalised in memory)
-                            c.yp, c.ldy = c.out.ptr(), c.out.ld
-                        else:
-                            c.yp, c.ldy = c.dyp, c.lddy
-                        c.coef = torch.empty(4 * c.cout, **f32)
-                        c.part = torch.empty(max(nblk, lib.yh_bn_bwd_blocks(M, c.cout)) * 2 * c.cout, **f32)
-
-                if r.fwd2:
-                    if r.pair_first:      # both siblings in one launch, at the first one's position in the list
-                        nblk = lib.yh_conv_pw_blocks(M, r.cin, r.cout + r.pair.cout)
-                        alloc_out(r, nblk)
-                        alloc_out(r.pair, nblk)
-                        q = r.pair
-                        # on the main lane whatever lane the record was traced on: both siblings' BN passes depend on it
-                        fwd.append(_op(L.OP_CONV_PW_FWD2, p=[r.x.ptr(), r.wf, r.bias, r.yp, r.part, q.bias, q.yp, q.part],
-                                       i=[r.x.ld, r.ldwf, r.ldy, r.x.B, r.x.H, r.x.W, r.cin, r.cout, q.ldy, q.cout], lane=0))
-                        if r.x_fused:
-                            _set_prologue(fwd[-1], r.x)
-                        if deferred_fork:
-                            fwd.append(_op(L.OP_FORK))
-                            deferred_fork = False
-                        elif ln == 1 or q.lane == 1:
-                            raise NotImplementedError("fused sibling convolution traced on the side lane without a preceding fork")
-                else:
-                    nblk = lib.yh_conv_narrow_blocks(r.x.B, r.x.H, r.x.W, r.cin, r.s) if r.narrow_f else \
-                        lib.yh_conv_s2_blocks(r.x.B, r.x.H, r.x.W, r.cout) if r.s2l_f else \
-                        lib.yh_conv_wino_blocks(r.x.B, r.x.H, r.x.W) if r.wino_f else \
-                        lib.yh_conv_pw_blocks(M, r.cin, r.cout) if r.pw_f else \
-                        lib.yh_conv_fwd_blocks(r.x.B, r.x.H, r.x.W, r.cout, r.k, r.s)
-                    alloc_out(r, nblk)
-                    ytarget, ldy = (r.yp, r.ldy) if r.bn is not None else (None, r.out.ld)
-                    if r.narrow_f:
-                        fwd.append(_op(L.OP_CONV_NARROW,
-                                       p=[r.x.ptr(), r.wf, r.bias, ytarget if ytarget is not None else r.out.ptr(),
-                                          r.part if r.bn is not None else None],
-                                       i=[r.x.ld, r.ldwf, ldy, r.x.B, r.x.H, r.x.W, r.cin, r.cout, r.s, 0, 0], lane=ln))
-                    else:
-                        fwd.append(_op(L.OP_CONV_S2_FWD if r.s2l_f else L.OP_CONV_WINO_FWD if r.wino_f else (L.OP_CONV_PW_FWD if r.pw_f else L.OP_CONV_FWD),
-                                       p=[r.x.ptr(), r.wf, r.bias, ytarget if ytarget is not None else r.out.ptr(),
-                                          r.part if r.bn is not None else None],
-                                       i=[r.x.ld, r.ldwf, ldy, r.x.B, r.x.H, r.x.W, r.cin, r.cout, r.k, r.s], lane=ln))
-                    if r.x_fused:                             # the input's BatchNorm + SiLU is applied while this kernel stages it
-                        _set_prologue(fwd[-1], r.x)
-                nblk = r.nblk
-                if r.bn is not None:
-                    track = r.bn.track_running_stats and r.bn.running_mean is not None
-                    mom = r.bn.momentum if r.bn.momentum is not None else 0.1
-                    fwd.append(_op(L.OP_BN_FINALIZE,
-                                   p=[r.part, r.bn.weight, r.bn.bias, r.bn.running_mean if track else None,
-                                      r.bn.running_var if track else None, r.coef,
-                                      r.bn.num_batches_tracked if track else None,
-                                      r.out.icoef_ptr(0) if r.virtual else None, r.out.icoef_ptr(1) if r.virtual else None],
-                                   i=[nblk, r.cout], f=[mom, r.bn.eps], l=[M], lane=ln))
-                    if not r.virtual:
-                        rf = self._res_fused(r)               # the residual is a raw conv output: normalised on the fly
-                        fwd.append(_op(L.OP_BN_SILU_FWD,
-                                       p=[r.yp, r.coef, r.residual.ptr() if r.residual else None, r.out.ptr(),
-                                          r.residual.icoef_ptr() if rf else None],
-                                       i=[r.ldy, r.residual.ld if r.residual else 0, r.out.ld, r.cout, r.Ho, r.Wo,
-                                          int(r.upsample), r.residual.icoef_ld if rf else 0], l=[M], lane=ln))
-            else:
-                if r.fused:
-                    continue
-                if not self.training and lib.yh_sppf_pool3_ok(r.x.H, r.x.W):
-                    # eval: SPPF's cascade pool5(pool5(pool5(x))) as one launch (no argmax, the plane stays in LDS)
-                    nxt = self.recs[ri + 1: ri + 3]
-                    if len(nxt) == 2 and all(isinstance(q, PoolRec) and q.lane == ln for q in nxt) \
-                            and _same_view(nxt[0].x, r.out) and _same_view(nxt[1].x, nxt[0].out) \
-                            and r.out.ld == nxt[0].out.ld == nxt[1].out.ld \
-                            and all(v.ptr() % 16 == 0 for v in (r.out, nxt[0].out, nxt[1].out)):
-                        fwd.append(_op(L.OP_SPPF_POOL3, p=[r.x.ptr(), r.out.ptr(), nxt[0].out.ptr(), nxt[1].out.ptr()],
-                                       i=[r.x.ld, r.out.ld, r.x.B, r.x.H, r.x.W, r.x.C], lane=ln))
-                        nxt[0].fused = nxt[1].fused = True
-                        continue
-                r.arg = torch.empty(r.x.B, r.x.H, r.x.W, r.x.C, device=dev, dtype=torch.uint8)
-                fwd.append(_op(L.OP_MAXPOOL5_FWD, p=[r.x.ptr(), r.out.ptr(), r.arg],
-                               i=[r.x.ld, r.out.ld, r.x.B, r.x.H, r.x.W, r.x.C], lane=ln))
-        import struct
-        head: List[L.YhOp] = list(reversed(s2m_packs))     # weight transforms: head of the forward list (training) / prep list (eval)
-        if pwpacks:
-            blob = b"".join(struct.pack("<QQQiiiiii", *d) for d in pwpacks)
-            self.pw_table = torch.frombuffer(bytearray(blob), dtype=torch.uint8).to(dev)
-            head.insert(0, _op(L.OP_PW_PACK_MULTI, p=[self.pw_table], i=[len(pwpacks)]))
-        if latpacks:
-            blob = b"".join(struct.pack("<QQiiii", *d) for d in latpacks)
-            self.lat_table = torch.frombuffer(bytearray(blob), dtype=torch.uint8).to(dev)
-            head.insert(0, _op(L.OP_LAT_PACK_MULTI, p=[self.lat_table], i=[len(latpacks)]))
-        if winos:
-            blob = b"".join(struct.pack("<QQiiii", *d) for d in winos)
-            self.wino_table = torch.frombuffer(bytearray(blob), dtype=torch.uint8).to(dev)
-            head.insert(0, _op(L.OP_WINO_WEIGHTS_MULTI, p=[self.wino_table], i=[len(winos)]))
-        if packs:   # every conv's OIHW -> packed copies in ONE launch
-            blob = b"".join(struct.pack("<QQQiiiiiiii", *d, 0, 0) for d in packs)
-            self.pack_table = torch.frombuffer(bytearray(blob), dtype=torch.uint8).to(dev)
-            head.insert(0, _op(L.OP_PACK_WEIGHTS_MULTI, p=[self.pack_table], i=[len(packs)]))
-        if folds:
-            # eval: BatchNorm folding + the transforms of the folded weights read only parameters and running statistics:
-            # they run once per weight state (refresh_folded_weights), not once per forward -- at batch 1 the fold was the
-            # longest launch of the pass
-            blob = b"".join(struct.pack("<QQQQQQQQiifi", *d) for d in folds)
-            self.fold_table = torch.frombuffer(bytearray(blob), dtype=torch.uint8).to(dev)
-            head.insert(0, _op(L.OP_FOLD_OIHW_MULTI, p=[self.fold_table], i=[len(folds)]))
-            self.prep_ops = _pack(head)
-        else:
-            fwd = head + fwd
-        self.fwd_ops = _pack(fwd)
-        self.bwd_ops = _pack(self._lower_backward(grad_of, keep)) if self.training else None
-        self._keep = keep
-        self._grad_of = grad_of
-        self.param_ptrs = self._signature()
-
-    # ---- bf16 lowering (BASELINE configs 3-4) -------------------------------------------------------------------------
-    def _compile_bf16(self, grad_of):
-        """One kernel family for every convolution: yh_bf16_conv_fwd / _bwd_data / _bwd_weight (bf16 operands, fp32
-        accumulation), bf16 BN+SiLU / pool passes, fp32 statistics and parameter gradients."""
-        import struct
-        lib = L.lib()
-        dev = self.device
-        f32 = dict(device=dev, dtype=torch.float32)
-        b16 = dict(device=dev, dtype=torch.bfloat16)
-        fwd: List[L.YhOp] = []
-        keep: List[torch.Tensor] = []
-        packs: List[tuple] = []
-        # sibling pointwise convs (C3 conv1 / conv2): one backward-data GEMM over K = Cout1 + Cout2, dx written once
-        if True:
-            groups: Dict[tuple, List[ConvRec]] = {}
-            for r in self.recs:
-                if isinstance(r, ConvRec) and r.k == 1 and r.s == 1 and r.bn is not None and r.cout % 8 == 0:
-                    groups.setdefault((id(r.x.buf), r.x.off, r.x.C), []).append(r)
-            for grp in groups.values():
-                if len(grp) == 2 and grp[0].cout == grp[1].cout and (self.need_input_grad or grp[0].x.buf is not self.input):
-                    grp[0].pair, grp[1].pair = grp[1], grp[0]
-                    grp[0].pair_first = True
-        for r in self.recs:
-            if isinstance(r, SyncRec):
+                if r.kind == "fork" and self._fork_deferred(ri + 1):
+                    continue            # the fused sibling conv runs on the main lane; the fork follows its launch
                 fwd.append(_op(L.OP_FORK if r.kind == "fork" else L.OP_JOIN))
-                continue
-            ln = r.lane
-            if isinstance(r, PoolRec):
-                r.arg = torch.empty(r.x.B, r.x.H, r.x.W, r.x.C, device=dev, dtype=torch.uint8)
-                fwd.append(_op(L.OP_BF16_MAXPOOL5_FWD, p=[r.x.ptr(), r.out.ptr(), r.arg],
-                               i=[r.x.ld, r.out.ld, r.x.B, r.x.H, r.x.W, r.x.C], lane=ln))
-                continue
-            kk = r.k * r.k
-            cin_real = r.weight.shape[1]
-            r.need_dx = self.need_input_grad or r.x.buf is not self.input
-            r.ldwf, r.ldwb = _rup8(r.cout), _rup8(r.cin)
-            r.wf = torch.empty(kk * r.cin * r.ldwf, **b16)
-            kpad = _rup8(r.cout)
-            koff = 0
-            if r.need_dx:
-                if r.pair is not None:
-                    kpad = r.cout + r.pair.cout
-                    if r.pair_first:
-                        r.wb = r.pair.wb = torch.zeros(kpad * r.ldwb, **b16)
-                    else:
-                        koff = r.pair.cout
-                else:
-                    r.wb = torch.zeros(kk * kpad * r.ldwb, **b16)
-            packs.append((r.weight.data_ptr(), r.wf.data_ptr(), r.wb.data_ptr() if r.need_dx else 0, r.cout, cin_real, kk,
-                          r.cin, r.ldwf, r.ldwb, koff, kpad))
-            M = r.x.B * r.Ho * r.Wo
-            r.nblk = lib.yh_bf16_conv_fwd_blocks(r.x.B, r.x.H, r.x.W, r.cin, r.cout, r.k, r.s, 0 if r.bn is not None else 1, r.x.ld,
-                                                 r.cout if r.bn is not None else r.out.ld)
-            # narrow high-resolution 3x3 layers (first layer, stem[3], the 16-channel bottleneck): the direct kernels of the fp32
-            # path with bf16 storage (conv_narrow.hip); cin_k = channels the kernel reads (4 of the first layer's 8 padded ones)
-            use_nar = r.k == 3 and r.bn is not None and r.x.ld % 4 == 0 and r.x.off % 4 == 0
-            r.cin_k = 4 if (cin_real <= 4 and r.cin == 8) else r.cin
-            # measured at batch 64 (tools/layer_bench.py --dtype bf16, ms narrow / generic bf16): first layer forward 0.250 /
-            # 0.358 and weight gradient 0.220 / 0.541; stem[3] forward 0.250 / 0.114, backward-data 0.295 / 0.338, weight gradient
-            # 0.274 / 0.155; 16 -> 16 forward 0.098 / 0.098, backward-data 0.114 / 0.099, weight gradient 0.113 / 0.129 per layer
-            # (8-byte pieces: twice the load instructions per byte of the fp32 form -- these kernels are bound by instruction
-            # issue and latency, not by bytes).  Each pass takes the faster kernel; YH_BF16_NARROW=all forces the narrow ones.
-            every = False
-            # round 3: stem[3] forward (16 -> 32, stride 2) has a bf16-MFMA form of the narrow kernel (0.112 -> 0.075 ms)
-            stem3 = r.s == 2 and r.cin == 16 and r.cout == 32 and r.cin == cin_real and r.x.ld % 8 == 0
-            r.narrow_f = bool(use_nar and (r.cin_k == 4 or stem3 or (every and r.cin == cin_real)) and lib.yh_conv_narrow_ok(r.cin_k, r.cout, 3, r.s))
-            r.narrow_w = bool(use_nar and (r.cin_k == 4 or r.s == 1 or every) and
-                              lib.yh_conv_narrow_bwd_weight_ok(r.cin_k, min(cin_real, r.cin_k), r.cout, 3, r.s))
-            r.narrow_b = bool(use_nar and r.need_dx and r.pair is None and r.cin == cin_real and
-                              ((r.s == 1 and every and lib.yh_conv_narrow_ok(r.cout, r.cin, 3, 1)) or
-                               (r.s == 2 and lib.yh_conv_narrow_dgrad_s2_ok(r.cin, r.cout))))
-            if r.narrow_f:
-                r.nblk = lib.yh_conv_narrow_blocks(r.x.B, r.x.H, r.x.W, r.cin_k, r.s)
-            if r.bn is not None:
-                r.y = torch.empty(r.x.B, r.Ho, r.Wo, r.cout, **b16)
-                r.coef = torch.empty(4 * r.cout, **f32)
-                r.part = torch.empty(max(r.nblk, lib.yh_bn_bwd_blocks(M, r.cout)) * 2 * r.cout, **f32)
-                if r.narrow_f:
-                    fwd.append(_op(L.OP_BF16_CONV_NARROW, p=[r.x.ptr(), r.wf, r.bias, r.y, r.part],
-                                   i=[r.x.ld, r.ldwf, r.cout, r.x.B, r.x.H, r.x.W, r.cin_k, r.cout, r.s, 0, 0, r.cin], lane=ln))
-                else:
-                    fwd.append(_op(L.OP_BF16_CONV_FWD, p=[r.x.ptr(), r.wf, r.bias, r.y, r.part],
-                                   i=[r.x.ld, r.ldwf, r.cout, r.x.B, r.x.H, r.x.W, r.cin, r.cout, r.k, r.s, 0], lane=ln))
-                track = r.bn.track_running_stats and r.bn.running_mean is not None
-                mom = r.bn.momentum if r.bn.momentum is not None else 0.1
-                fwd.append(_op(L.OP_BN_FINALIZE,
-                               p=[r.part, r.bn.weight, r.bn.bias, r.bn.running_mean if track else None,
-                                  r.bn.running_var if track else None, r.coef, r.bn.num_batches_tracked if track else None,
-                                  None, None],
-                               i=[r.nblk, r.cout], f=[mom, r.bn.eps], l=[M], lane=ln))
-                fwd.append(_op(L.OP_BF16_BN_SILU_FWD,
-                               p=[r.y, r.coef, r.residual.ptr() if r.residual else None, r.out.ptr()],
-                               i=[r.cout, r.residual.ld if r.residual else 0, r.out.ld, r.cout, r.Ho, r.Wo, int(r.upsample)],
-                               l=[M], lane=ln))
-            else:       # head output: fp32, no BatchNorm
-                fwd.append(_op(L.OP_BF16_CONV_FWD, p=[r.x.ptr(), r.wf, r.bias, r.out.ptr(), None],
-                               i=[r.x.ld, r.ldwf, r.out.ld, r.x.B, r.x.H, r.x.W, r.cin, r.cout, r.k, r.s, 1], lane=ln))
-        blob = b"".join(struct.pack("<QQQiiiiiiii", *d) for d in packs)
-        self.pack_table = torch.frombuffer(bytearray(blob), dtype=torch.uint8).to(dev)
-        fwd.insert(0, _op(L.OP_BF16_PACK_MULTI, p=[self.pack_table], i=[len(packs)]))
-        self.fwd_ops = _pack(fwd)
-        self.bwd_ops = _pack(self._lower_backward_bf16(grad_of))
-        self._keep = keep
-        self._grad_of = grad_of
-        self.param_ptrs = self._signature()
+            elif isinstance(r, ConvRec):
+                lower_conv(ri, r, fwd, rows)
+            elif not r.fused:
+                self._lower_pool(ri, r, fwd)
+        return fwd
 
-    def _lower_backward_bf16(self, grad_of) -> List[L.YhOp]:
+    def _fork_deferred(self, ri: int) -> bool:
+        r = self.recs[ri] if ri < len(self.recs) else None
+        return isinstance(r, ConvRec) and r.fwd2 and r.pair_first and r.lane == 1
+
+    def _lower_pool(self, ri: int, r: PoolRec, fwd: List[L.YhOp]):
+        if not self.training and L.lib().yh_sppf_pool3_ok(r.x.H, r.x.W):
+            # eval: SPPF's cascade pool5(pool5(pool5(x))) as one launch (no argmax, the plane stays in LDS)
+            nxt = self.recs[ri + 1: ri + 3]
+            if len(nxt) == 2 and all(isinstance(q, PoolRec) and q.lane == r.lane for q in nxt) \
+                    and _same_view(nxt[0].x, r.out) and _same_view(nxt[1].x, nxt[0].out) \
+                    and r.out.ld == nxt[0].out.ld == nxt[1].out.ld \
+                    and all(v.ptr() % 16 == 0 for v in (r.out, nxt[0].out, nxt[1].out)):
+                fwd.append(_op(L.OP_SPPF_POOL3, p=[r.x.ptr(), r.out.ptr(), nxt[0].out.ptr(), nxt[1].out.ptr()],
+                               i=[r.x.ld, r.out.ld, r.x.B, r.x.H, r.x.W, r.x.C], lane=r.lane))
+                nxt[0].fused = nxt[1].fused = True
+                return
+        r.arg = torch.empty(r.x.B, r.x.H, r.x.W, r.x.C, device=self.device, dtype=torch.uint8)
+        fwd.append(_op(_OPS[self.bf16]["pool"], p=[r.x.ptr(), r.out.ptr(), r.arg], i=[r.x.ld, r.out.ld, r.x.B, r.x.H, r.x.W, r.x.C],
+                       lane=r.lane))
+
+    def _alloc_out(self, c: ConvRec, nblk: int, M: int):
+        """Raw conv output, BatchNorm coefficients and partial-sum scratch (nblk rows from the forward kernel)."""
+        if c.bn is not None and nblk <= 0:
+            raise RuntimeError(f"planner: no forward block geometry for a {c.x.B}x{c.x.H}x{c.x.W} {c.cin}->{c.cout} convolution")
+        c.nblk = nblk
+        if c.bn is not None and c.coef is None:
+            f32 = dict(device=self.device, dtype=torch.float32)
+            c.y = torch.empty(c.x.B, c.Ho, c.Wo, c.cout, device=self.device, dtype=self.act_dtype)
+            c.dyp, c.lddy = c.y.data_ptr(), c.cout
+            if c.virtual:                         # the raw output lives in the output view itself (never normalised in memory)
+                c.yp, c.ldy = c.out.ptr(), c.out.ld
+            else:
+                c.yp, c.ldy = c.dyp, c.lddy
+            c.coef = torch.empty(4 * c.cout, **f32)
+            c.part = torch.empty(max(nblk, L.lib().yh_bn_bwd_blocks(M, c.cout)) * 2 * c.cout, **f32)
+
+    @staticmethod
+    def _bn_finalize(r: ConvRec, M: int) -> L.YhOp:
+        """Batch statistics from the forward's partial sums -> scale / shift in r.coef (and in the readers' prologue table when the
+        output is virtual), running statistics updated."""
+        bn = r.bn
+        track = bn.track_running_stats and bn.running_mean is not None
+        return _op(L.OP_BN_FINALIZE,
+                   p=[r.part, bn.weight, bn.bias, bn.running_mean if track else None, bn.running_var if track else None, r.coef,
+                      bn.num_batches_tracked if track else None,
+                      r.out.icoef_ptr(0) if r.virtual else None, r.out.icoef_ptr(1) if r.virtual else None],
+                   i=[r.nblk, r.cout], f=[bn.momentum if bn.momentum is not None else 0.1, bn.eps], l=[M], lane=r.lane)
+
+    def _lower_conv_eval(self, ri: int, r: ConvRec, fwd: List[L.YhOp], rows: Dict[int, list]):
+        """BatchNorm is folded into an OIHW copy of the weights (yh_fold_oihw_multi), which then goes through the weight transform
+        of the layer's kernel family."""
         lib = L.lib()
-        if grad_of is None:
-            raise ValueError("training plan needs gradient destinations")
-        for b in self.buffers:
-            b.grad_cover = []
-        for v, _ in self.outputs:
-            v.buf.grad_cover.append((v.off, v.off + v.C))
-        ws_floats = 1
-        for r in self.recs:
-            if isinstance(r, ConvRec):
-                ws_floats = max(ws_floats, lib.yh_conv_narrow_bwd_weight_ws(r.x.B, r.x.H, r.x.W, r.cin_k, r.cout, r.s) if r.narrow_w else
-                                lib.yh_bf16_conv_bwd_weight_ws(r.x.B, r.x.H, r.x.W, r.cin, r.cout, r.k, r.s))
-                if r.bias is not None:
-                    ws_floats = max(ws_floats, lib.yh_colsum_ws(r.x.B * r.Ho * r.Wo, r.cout))
-        self.ws = torch.empty(int(ws_floats), device=self.device, dtype=torch.float32)
-        ops: List[L.YhOp] = []
-        pair_pending = set()
-        self.grad_ready = {}
-        for r in reversed(self.recs):
-            if isinstance(r, SyncRec):
-                continue
-            if isinstance(r, PoolRec):
-                dst, acc = self._grad_target(r.x)
-                if not acc:
-                    raise NotImplementedError("max-pool backward expects an already written input gradient")
-                ops.append(_op(L.OP_BF16_MAXPOOL5_BWD, p=[r.out.gptr(), r.arg, dst], i=[r.out.ldg, r.x.ldg, r.x.B, r.x.H, r.x.W, r.x.C]))
-                continue
-            M = r.x.B * r.Ho * r.Wo
-            if r.bn is not None:
-                nb = lib.yh_bn_bwd_blocks(M, r.cout)
-                ops.append(_op(L.OP_BF16_BN_SILU_BWD_REDUCE, p=[r.out.gptr(), r.y, r.coef, r.part],
-                               i=[r.out.ldg, r.cout, r.cout, r.Ho, r.Wo, int(r.upsample)], l=[M]))
-                if r.residual is not None:
-                    dres, racc = self._grad_target(r.residual)
-                    ldres = r.residual.ldg
-                else:
-                    dres, racc, ldres = None, 0, 0
-                ops.append(_op(L.OP_BF16_BN_SILU_BWD_APPLY,
-                               p=[r.out.gptr(), r.y, r.coef, r.part, r.bn.weight, grad_of[id(r.bn.weight)], grad_of[id(r.bn.bias)],
-                                  r.y, dres],
-                               i=[r.out.ldg, r.cout, nb, r.cout, ldres, racc, r.cout, r.Ho, r.Wo, int(r.upsample)], l=[M]))
-                dy, lddy, kcout = r.y.data_ptr(), r.cout, r.cout
-                self.grad_ready[id(r.bn.weight)] = self.grad_ready[id(r.bn.bias)] = len(ops)
-            else:       # head: the loss wrote a bf16 gradient zero-padded to a multiple of 8 channels
-                dy, lddy, kcout = r.out.gptr(), r.out.ldg, _rup8(r.cout)
-                if r.out.off != 0 or r.out.ldg != kcout:
-                    raise NotImplementedError("head gradient must own its (padded) buffer")
-            fuse_bias = r.bias is not None and r.narrow_w and r.bn is not None
-            if r.bias is not None and not fuse_bias:
-                # head biases (18 / 255 channels): sum the zero-padded multiple of 4 so the vector kernel applies; the extra
-                # column sums are exact zeros and land in the 4-float padding every tensor has in the flat gradient buffer
-                cs = _rup4(r.cout) if (r.bn is None and _rup4(r.cout) <= lddy) else r.cout
-                ops.append(_op(L.OP_BF16_COLSUM, p=[dy, grad_of[id(r.bias)], self.ws], i=[lddy, cs], l=[M]))
-                self.grad_ready[id(r.bias)] = len(ops)
-            if r.narrow_w:
-                ops.append(_op(L.OP_BF16_CONV_NARROW_BWD_WEIGHT,
-                               p=[r.x.ptr(), dy, grad_of[id(r.weight)], self.ws, grad_of[id(r.bias)] if fuse_bias else None],
-                               i=[r.x.ld, lddy, r.x.B, r.x.H, r.x.W, r.cin_k, min(r.weight.shape[1], r.cin_k), r.cout, r.k, r.s],
-                               l=[self.ws.numel()]))
+        f32 = dict(device=self.device, dtype=torch.float32)
+        bn, kk, cin_real = r.bn, r.k * r.k, r.weight.shape[1]
+        fbias = torch.empty(r.cout, **f32)
+        wfold = torch.empty(r.cout * cin_real * kk, **f32)
+        self._keep += [fbias, wfold]
+        rows[L.OP_FOLD_OIHW_MULTI].append(
+            (r.weight.data_ptr(), r.bias.data_ptr() if r.bias is not None else 0, bn.weight.data_ptr() if bn is not None else 0,
+             bn.bias.data_ptr() if bn is not None else 0, bn.running_mean.data_ptr() if bn is not None else 0,
+             bn.running_var.data_ptr() if bn is not None else 0, wfold.data_ptr(), fbias.data_ptr(),
+             r.cout, cin_real * kk, float(bn.eps) if bn is not None else 0.0, 0))
+        l, extra = [], []
+        if r.eval_fam == "lat":
+            kind, r.wf = L.OP_CONV_LAT_FWD_FUSED, torch.zeros(kk * r.cin * r.ldwf, **f32)
+            rows[L.OP_LAT_PACK_MULTI].append((wfold.data_ptr(), r.wf.data_ptr(), r.cout, cin_real, kk, r.ldwf))
+        elif r.eval_fam == "wino":
+            kind, r.wf = L.OP_CONV_WINO_FWD_FUSED, torch.empty(16 * r.cin * r.ldwf, **f32)
+            rows[L.OP_WINO_WEIGHTS_MULTI].append((wfold.data_ptr(), r.wf.data_ptr(), r.cout, cin_real, r.ldwf, 0))
+        elif r.eval_fam == "pw":
+            kind, r.wf = L.OP_CONV_PW_FWD_FUSED, torch.zeros(r.cin * r.ldwf, **f32)
+            rows[L.OP_PW_PACK_MULTI].append((wfold.data_ptr(), r.wf.data_ptr(), 0, r.cout, r.cin, r.ldwf, r.ldwb, 0, 0))
+        else:
+            kind, r.wf = L.OP_CONV_FWD_FUSED, torch.empty(kk * r.cin * r.ldwf, **f32)
+            rows[L.OP_PACK_WEIGHTS_MULTI].append((wfold.data_ptr(), r.wf.data_ptr(), 0, r.cout, cin_real, kk, r.cin, r.ldwf, r.ldwb, 0, 0))
+            nws = int(lib.yh_conv_fwd_fused_ws(r.x.B, r.x.H, r.x.W, r.cin, r.cout, r.k, r.s))
+            sws = torch.zeros(nws, **f32) if nws > 0 else None   # per layer (two lanes may run split layers at once); zero tickets
+            if sws is not None:
+                self._keep.append(sws)
+            l, extra = [nws], [sws]
+        fwd.append(_op(kind, p=[r.x.ptr(), r.wf, fbias, r.residual.ptr() if r.residual else None, r.out.ptr()] + extra, l=l,
+                       i=[r.x.ld, r.ldwf, r.residual.ld if r.residual else 0, r.out.ld, r.x.B, r.x.H, r.x.W,
+                          r.cin, r.cout, r.k, r.s, int(bn is not None), int(r.upsample)], lane=r.lane))
+
+    def _lower_conv_f32(self, ri: int, r: ConvRec, fwd: List[L.YhOp], rows: Dict[int, list]):
+        lib = L.lib()
+        f32 = dict(device=self.device, dtype=torch.float32)
+        kk = r.k * r.k
+        second = r.pair is not None and not r.pair_first
+        # forward weights, in the layout of the forward's kernel family
+        if r.fwd2 and second:
+            pass                                      # shares its sibling's matrix
+        elif r.pw_f:                                  # the pointwise pack writes only the conv's own columns
+            if r.fwd2:
+                r.ldwf = r.pair.ldwf = _rup4(r.cout + r.pair.cout)
+            r.wf = torch.zeros(r.cin * r.ldwf, **f32)
+            if r.fwd2:
+                r.pair.wf = r.wf
+        elif r.wino_f:
+            r.wf = torch.empty(16 * r.cin * r.ldwf, **f32)
+        elif r.s2l_f:
+            r.wf = torch.zeros(kk * r.cin * r.ldwf, **f32)
+        else:
+            r.wf = torch.empty(kk * r.cin * r.ldwf, **f32)
+        # backward-data weights
+        if r.pair_first:          # stacked backward packs: rows [0, c1) this conv, [c1, c1 + c2) its sibling
+            stacked = torch.empty((r.cout + r.pair.cout) * r.ldwb, **f32)
+            if r.pw_b:            # one k-quad interleaved matrix for both: each record writes its own K rows
+                r.wb = r.pair.wb = stacked
             else:
-                ops.append(_op(L.OP_BF16_CONV_BWD_WEIGHT, p=[r.x.ptr(), dy, grad_of[id(r.weight)], self.ws],
-                               i=[r.x.ld, lddy, r.x.B, r.x.H, r.x.W, r.cin, r.weight.shape[1], r.cout, r.k, r.s], l=[self.ws.numel()]))
-            self.grad_ready[id(r.weight)] = len(ops)
-            if fuse_bias:
-                self.grad_ready[id(r.bias)] = len(ops)
-            if not r.need_dx:
-                continue
+                r.wb, r.pair.wb = stacked[: r.cout * r.ldwb], stacked[r.cout * r.ldwb:]
+            self._keep.append(stacked)
+        elif r.s2m_b:
+            r.ldwb = _rup4(2 * r.cin)
+            r.wb = torch.empty(6 * r.cout * r.ldwb, **f32)
+            rows[L.OP_PACK_WEIGHTS_S2M].append(_op(L.OP_PACK_WEIGHTS_S2M, p=[r.weight, r.wb], i=[r.cout, r.cin, r.ldwb]))
+        elif r.need_dx and r.pair is None:
+            # K rows of the backward pack: a 1x1 head reads dY rows zero-padded to a multiple of 4 channels against zero rows here
+            r.kcout_b = _rup4(r.cout) if (r.bn is None and r.k == 1 and not (r.wino_b or r.pw_b) and r.out.ldg >= _rup4(r.cout)) else r.cout
+            r.wb = (torch.zeros if r.kcout_b != r.cout else torch.empty)((16 if r.wino_b else kk) * r.kcout_b * r.ldwb, **f32)
+        if r.pw_f or r.pw_b:
+            rows[L.OP_PW_PACK_MULTI].append((r.weight.data_ptr(), r.wf.data_ptr() if r.pw_f else 0, r.wb.data_ptr() if r.pw_b else 0,
+                                             r.cout, r.cin, r.ldwf, r.ldwb, r.pair.cout if second else 0,
+                                             r.pair.cout if (second and r.fwd2) else 0))
+        if r.wino_f:
+            rows[L.OP_WINO_WEIGHTS_MULTI].append((r.weight.data_ptr(), r.wf.data_ptr(), r.cout, r.weight.shape[1], r.ldwf, 0))
+        if r.wino_b:
+            rows[L.OP_WINO_WEIGHTS_MULTI].append((r.weight.data_ptr(), r.wb.data_ptr(), r.cout, r.weight.shape[1], r.ldwb, 1))
+        if r.s2l_f:
+            rows[L.OP_LAT_PACK_MULTI].append((r.weight.data_ptr(), r.wf.data_ptr(), r.cout, r.weight.shape[1], kk, r.ldwf))
+        gen_f = not (r.wino_f or r.pw_f or r.s2l_f)            # layouts the generic pack kernel still has to write
+        gen_b = r.wb is not None and not (r.wino_b or r.pw_b or r.s2m_b)
+        if gen_f or gen_b:
+            rows[L.OP_PACK_WEIGHTS_MULTI].append((r.weight.data_ptr(), r.wf.data_ptr() if gen_f else 0, r.wb.data_ptr() if gen_b else 0,
+                                                  r.cout, r.weight.shape[1], kk, r.cin, r.ldwf, r.ldwb, 0, 0))
+        M = r.x.B * r.Ho * r.Wo
+        if r.fwd2:
+            if r.pair_first:      # both siblings in one launch, at the first one's position in the list
+                q = r.pair
+                nblk = lib.yh_conv_pw_blocks(M, r.cin, r.cout + q.cout)
+                self._alloc_out(r, nblk, M)
+                self._alloc_out(q, nblk, M)
+                # on the main lane whatever lane the record was traced on: both siblings' BN passes depend on it
+                fwd.append(_op(L.OP_CONV_PW_FWD2, p=[r.x.ptr(), r.wf, r.bias, r.yp, r.part, q.bias, q.yp, q.part],
+                               i=[r.x.ld, r.ldwf, r.ldy, r.x.B, r.x.H, r.x.W, r.cin, r.cout, q.ldy, q.cout], lane=0))
+                if r.x_fused:
+                    _set_prologue(fwd[-1], r.x)
+                prev = self.recs[ri - 1] if ri else None
+                if r.lane == 1 and isinstance(prev, SyncRec) and prev.kind == "fork":
+                    fwd.append(_op(L.OP_FORK))        # deferred by _lower_forward
+                elif r.lane == 1 or q.lane == 1:
+                    raise NotImplementedError("fused sibling convolution traced on the side lane without a preceding fork")
+        else:
+            nblk = lib.yh_conv_narrow_blocks(r.x.B, r.x.H, r.x.W, r.cin, r.s) if r.narrow_f else \
+                lib.yh_conv_s2_blocks(r.x.B, r.x.H, r.x.W, r.cout) if r.s2l_f else \
+                lib.yh_conv_wino_blocks(r.x.B, r.x.H, r.x.W) if r.wino_f else \
+                lib.yh_conv_pw_blocks(M, r.cin, r.cout) if r.pw_f else \
+                lib.yh_conv_fwd_blocks(r.x.B, r.x.H, r.x.W, r.cout, r.k, r.s)
+            self._alloc_out(r, nblk, M)
+            yt, ldy = (r.yp, r.ldy) if r.bn is not None else (r.out.ptr(), r.out.ld)
+            p = [r.x.ptr(), r.wf, r.bias, yt, r.part if r.bn is not None else None]
+            if r.narrow_f:
+                fwd.append(_op(L.OP_CONV_NARROW, p=p, i=[r.x.ld, r.ldwf, ldy, r.x.B, r.x.H, r.x.W, r.cin, r.cout, r.s, 0, 0], lane=r.lane))
+            else:
+                kind = L.OP_CONV_S2_FWD if r.s2l_f else L.OP_CONV_WINO_FWD if r.wino_f else L.OP_CONV_PW_FWD if r.pw_f else L.OP_CONV_FWD
+                fwd.append(_op(kind, p=p, i=[r.x.ld, r.ldwf, ldy, r.x.B, r.x.H, r.x.W, r.cin, r.cout, r.k, r.s], lane=r.lane))
+            if r.x_fused:                             # the input's BatchNorm + SiLU is applied while this kernel stages it
+                _set_prologue(fwd[-1], r.x)
+        if r.bn is not None:
+            fwd.append(self._bn_finalize(r, M))
+            if not r.virtual:
+                rf = self._res_fused(r)               # the residual is a raw conv output: normalised on the fly
+                fwd.append(_op(L.OP_BN_SILU_FWD,
+                               p=[r.yp, r.coef, r.residual.ptr() if r.residual else None, r.out.ptr(),
+                                  r.residual.icoef_ptr() if rf else None],
+                               i=[r.ldy, r.residual.ld if r.residual else 0, r.out.ld, r.cout, r.Ho, r.Wo,
+                                  int(r.upsample), r.residual.icoef_ld if rf else 0], l=[M], lane=r.lane))
+
+    def _lower_conv_bf16(self, ri: int, r: ConvRec, fwd: List[L.YhOp], rows: Dict[int, list]):
+        lib = L.lib()
+        b16 = dict(device=self.device, dtype=torch.bfloat16)
+        kk, cin_real = r.k * r.k, r.weight.shape[1]
+        r.wf = torch.empty(kk * r.cin * r.ldwf, **b16)
+        kpad, koff = _rup8(r.cout), 0
+        if r.need_dx:
             if r.pair is not None:
-                if id(r.pair) in pair_pending:      # second of the pair in backward order: both dY are final now
-                    first, second = (r, r.pair) if r.pair_first else (r.pair, r)
-                    dst, acc = self._grad_target(r.x)
-                    ops.append(_op(L.OP_BF16_CONV_BWD_DATA, p=[first.y, first.wb, dst, second.y],
-                                   i=[first.cout, first.ldwb, r.x.ldg, r.x.B, r.x.H, r.x.W, r.cin, first.cout + second.cout, 1, 1,
-                                      acc, first.cout]))
+                kpad = r.cout + r.pair.cout
+                if r.pair_first:
+                    r.wb = r.pair.wb = torch.zeros(kpad * r.ldwb, **b16)
                 else:
-                    pair_pending.add(id(r))
-                continue
-            dst, acc = self._grad_target(r.x)
-            if r.narrow_b and r.s == 1:      # x = dY (Cout channels), output = dX (Cin channels), backward pack, flipped taps
-                ops.append(_op(L.OP_BF16_CONV_NARROW, p=[dy, r.wb, None, dst, None],
-                               i=[lddy, r.ldwb, r.x.ldg, r.x.B, r.x.H, r.x.W, r.cout, r.cin, 1, 1, acc, _rup8(r.cout)]))
-            elif r.narrow_b:
-                ops.append(_op(L.OP_BF16_CONV_NARROW_DGRAD_S2, p=[dy, r.wb, dst],
-                               i=[lddy, r.ldwb, r.x.ldg, r.x.B, r.x.H, r.x.W, r.cin, r.cout, r.k, r.s, acc, _rup8(r.cout)]))
+                    koff = r.pair.cout
             else:
-                ops.append(_op(L.OP_BF16_CONV_BWD_DATA, p=[dy, r.wb, dst, None],
-                               i=[lddy, r.ldwb, r.x.ldg, r.x.B, r.x.H, r.x.W, r.cin, kcout, r.k, r.s, acc, 0]))
-        return ops
+                r.wb = torch.zeros(kk * kpad * r.ldwb, **b16)
+        rows[L.OP_BF16_PACK_MULTI].append((r.weight.data_ptr(), r.wf.data_ptr(), r.wb.data_ptr() if r.need_dx else 0, r.cout, cin_real,
+                                           kk, r.cin, r.ldwf, r.ldwb, koff, kpad))
+        M = r.x.B * r.Ho * r.Wo
+        self._alloc_out(r, lib.yh_conv_narrow_blocks(r.x.B, r.x.H, r.x.W, r.cin_k, r.s) if r.narrow_f else
+                        lib.yh_bf16_conv_fwd_blocks(r.x.B, r.x.H, r.x.W, r.cin, r.cout, r.k, r.s, 0 if r.bn is not None else 1, r.x.ld,
+                                                    r.cout if r.bn is not None else r.out.ld), M)
+        if r.bn is None:        # head output: fp32, no BatchNorm
+            fwd.append(_op(L.OP_BF16_CONV_FWD, p=[r.x.ptr(), r.wf, r.bias, r.out.ptr(), None],
+                           i=[r.x.ld, r.ldwf, r.out.ld, r.x.B, r.x.H, r.x.W, r.cin, r.cout, r.k, r.s, 1], lane=r.lane))
+            return
+        if r.narrow_f:
+            fwd.append(_op(L.OP_BF16_CONV_NARROW, p=[r.x.ptr(), r.wf, r.bias, r.yp, r.part],
+                           i=[r.x.ld, r.ldwf, r.ldy, r.x.B, r.x.H, r.x.W, r.cin_k, r.cout, r.s, 0, 0, r.cin], lane=r.lane))
+        else:
+            fwd.append(_op(L.OP_BF16_CONV_FWD, p=[r.x.ptr(), r.wf, r.bias, r.yp, r.part],
+                           i=[r.x.ld, r.ldwf, r.ldy, r.x.B, r.x.H, r.x.W, r.cin, r.cout, r.k, r.s, 0], lane=r.lane))
+        fwd.append(self._bn_finalize(r, M))
+        fwd.append(_op(L.OP_BF16_BN_SILU_FWD, p=[r.yp, r.coef, r.residual.ptr() if r.residual else None, r.out.ptr()],
+                       i=[r.ldy, r.residual.ld if r.residual else 0, r.out.ld, r.cout, r.Ho, r.Wo, int(r.upsample)], l=[M], lane=r.lane))
 
     def _grad_target(self, v: View) -> Tuple[int, int]:
         """Pointer into the gradient tensor of `v` and whether the op must accumulate."""
@@ -924,8 +837,21 @@ class Plan:
         cov.append((lo, hi))
         return v.gptr(), 0
 
-    def _lower_backward(self, grad_of, keep) -> List[L.YhOp]:
+    def _wgrad_ws(self, r: ConvRec) -> int:
         lib = L.lib()
+        if r.narrow_w:
+            return lib.yh_conv_narrow_bwd_weight_ws(r.x.B, r.x.H, r.x.W, r.cin_k, r.cout, r.s)
+        if r.wino_w:
+            return lib.yh_conv_wino_bwd_weight_ws(r.x.B, r.x.H, r.x.W, r.cin, r.cout)
+        if r.pw_w:
+            return lib.yh_conv_pw_bwd_weight_ws(r.x.B * r.x.H * r.x.W, r.cin, r.cout)
+        return (lib.yh_bf16_conv_bwd_weight_ws if self.bf16 else lib.yh_conv_bwd_weight_ws)(r.x.B, r.x.H, r.x.W, r.cin, r.cout, r.k, r.s)
+
+    def _lower_backward(self, grad_of) -> List[L.YhOp]:
+        """The records in reverse: BatchNorm + SiLU backward (dY over Y), bias and weight gradients, backward-data into the input's
+        gradient (written or accumulated, see _grad_target).  One walk for fp32 and bf16 plans; _OPS holds the per-type op kinds."""
+        lib = L.lib()
+        K = _OPS[self.bf16]
         if grad_of is None:
             raise ValueError("training plan needs gradient destinations")
         for b in self.buffers:
@@ -934,20 +860,14 @@ class Plan:
         for v, _ in self.outputs:
             v.buf.grad_cover.append((v.off, v.off + v.C))
         ws_floats = 1
-        for r in self.recs:
-            if isinstance(r, ConvRec):
-                ws_floats = max(ws_floats, lib.yh_conv_narrow_bwd_weight_ws(r.x.B, r.x.H, r.x.W, r.cin, r.cout, r.s) if r.narrow_w else
-                                lib.yh_conv_wino_bwd_weight_ws(r.x.B, r.x.H, r.x.W, r.cin, r.cout) if r.wino_w else
-                                lib.yh_conv_pw_bwd_weight_ws(r.x.B * r.x.H * r.x.W, r.cin, r.cout) if r.pw_w else
-                                lib.yh_conv_bwd_weight_ws(r.x.B, r.x.H, r.x.W, r.cin, r.cout, r.k, r.s))
-                if r.bias is not None:
-                    ws_floats = max(ws_floats, lib.yh_colsum_ws(r.x.B * r.Ho * r.Wo, r.cout))
+        for r in self._convs():
+            ws_floats = max(ws_floats, self._wgrad_ws(r))
+            if r.bias is not None:
+                ws_floats = max(ws_floats, lib.yh_colsum_ws(r.x.B * r.Ho * r.Wo, r.cout))
         self.ws = torch.empty(int(ws_floats), device=self.device, dtype=torch.float32)
         ops: List[L.YhOp] = []
         pair_pending = set()
         self.grad_ready: Dict[int, int] = {}     # id(param) -> number of backward ops after which its grad is final
-        writers: List[tuple] = []                # (op index, view written, consumer rec | None): every op that writes an activation gradient
-        bn_ops: Dict[int, tuple] = {}            # id(rec) -> (rec, index of its REDUCE op, index of its APPLY op)
         for r in reversed(self.recs):
             if isinstance(r, SyncRec):
                 continue
@@ -955,82 +875,73 @@ class Plan:
                 dst, acc = self._grad_target(r.x)
                 if not acc:
                     raise NotImplementedError("max-pool backward expects an already written input gradient")
-                ops.append(_op(L.OP_MAXPOOL5_BWD, p=[r.out.gptr(), r.arg, dst], i=[r.out.ld, r.x.ld, r.x.B, r.x.H, r.x.W, r.x.C]))
-                writers.append((len(ops) - 1, r.x, None))
+                ops.append(_op(K["pool_bwd"], p=[r.out.gptr(), r.arg, dst], i=[r.out.ldg, r.x.ldg, r.x.B, r.x.H, r.x.W, r.x.C]))
                 continue
             M = r.x.B * r.Ho * r.Wo
             if r.bn is not None:
                 nb = lib.yh_bn_bwd_blocks(M, r.cout)
-                ops.append(_op(L.OP_BN_SILU_BWD_REDUCE, p=[r.out.gptr(), r.yp, r.coef, r.part],
-                               i=[r.out.ld, r.ldy, r.cout, r.Ho, r.Wo, int(r.upsample)], l=[M]))
-                if r.residual is not None:
-                    dres, racc = self._grad_target(r.residual)
-                    ldres = r.residual.ld
-                else:
-                    dres, racc, ldres = None, 0, 0
-                ops.append(_op(L.OP_BN_SILU_BWD_APPLY,
-                               p=[r.out.gptr(), r.yp, r.coef, r.part, r.bn.weight, grad_of[id(r.bn.weight)],
-                                  grad_of[id(r.bn.bias)], r.dyp, dres],
-                               i=[r.out.ld, r.ldy, nb, r.lddy, ldres, racc, r.cout, r.Ho, r.Wo, int(r.upsample)], l=[M]))
-                bn_ops[id(r)] = (r, len(ops) - 2, len(ops) - 1)
-                if r.residual is not None:
-                    writers.append((len(ops) - 1, r.residual, None))
-                dy, lddy = r.dyp, r.lddy
+                ops.append(_op(K["reduce"], p=[r.out.gptr(), r.yp, r.coef, r.part], i=[r.out.ldg, r.ldy, r.cout, r.Ho, r.Wo, int(r.upsample)],
+                               l=[M]))
+                dres, racc = self._grad_target(r.residual) if r.residual is not None else (None, 0)
+                ops.append(_op(K["apply"],
+                               p=[r.out.gptr(), r.yp, r.coef, r.part, r.bn.weight, grad_of[id(r.bn.weight)], grad_of[id(r.bn.bias)],
+                                  r.dyp, dres],
+                               i=[r.out.ldg, r.ldy, nb, r.lddy, r.residual.ldg if r.residual is not None else 0, racc, r.cout, r.Ho,
+                                  r.Wo, int(r.upsample)], l=[M]))
+                dy, lddy, kcout = r.dyp, r.lddy, r.cout
                 self.grad_ready[id(r.bn.weight)] = self.grad_ready[id(r.bn.bias)] = len(ops)
-            else:
-                dy, lddy = r.out.gptr(), r.out.ldg                 # head: the loss / autograd wrote rows zero-padded to ldg channels
-            kcout = (r.kcout_b or r.cout) if r.bn is None else r.cout
+            else:       # head: the loss / autograd wrote rows zero-padded to ldg channels
+                dy, lddy, kcout = r.out.gptr(), r.out.ldg, r.kcout_b or r.cout
             fuse_bias = r.bias is not None and r.narrow_w          # the narrow weight-gradient kernel also sums dY's columns
             if r.bias is not None and not fuse_bias:
                 # head biases: sum the zero-padded multiple of 4 so the vector kernel applies; the extra column sums are exact zeros
                 # and land in the 4-float padding every tensor has in the flat gradient buffer
                 cs = _rup4(r.cout) if (r.bn is None and _rup4(r.cout) <= lddy) else r.cout
-                ops.append(_op(L.OP_COLSUM, p=[dy, grad_of[id(r.bias)], self.ws], i=[lddy, cs], l=[M]))
+                ops.append(_op(K["colsum"], p=[dy, grad_of[id(r.bias)], self.ws], i=[lddy, cs], l=[M]))
                 self.grad_ready[id(r.bias)] = len(ops)
-            ops.append(_op(L.OP_CONV_NARROW_BWD_WEIGHT if r.narrow_w else L.OP_CONV_WINO_BWD_WEIGHT if r.wino_w else
-                           (L.OP_CONV_PW_BWD_WEIGHT if r.pw_w else L.OP_CONV_BWD_WEIGHT),
+            cin, cin_real = (r.cin_k, min(r.weight.shape[1], r.cin_k)) if r.narrow_w else (r.cin, r.weight.shape[1])
+            ops.append(_op(K["narrow_w"] if r.narrow_w else L.OP_CONV_WINO_BWD_WEIGHT if r.wino_w else
+                           L.OP_CONV_PW_BWD_WEIGHT if r.pw_w else K["wgrad"],
                            p=[r.x.ptr(), dy, grad_of[id(r.weight)], self.ws, grad_of[id(r.bias)] if fuse_bias else None],
-                           i=[r.x.ld, lddy, r.x.B, r.x.H, r.x.W, r.cin, r.weight.shape[1], r.cout, r.k, r.s],
-                           l=[self.ws.numel()]))
+                           i=[r.x.ld, lddy, r.x.B, r.x.H, r.x.W, cin, cin_real, r.cout, r.k, r.s], l=[self.ws.numel()]))
             if r.x_fused:                                          # x is a raw conv output: the kernel normalises it while staging
                 _set_prologue(ops[-1], r.x)
             self.grad_ready[id(r.weight)] = len(ops)
             if fuse_bias:
                 self.grad_ready[id(r.bias)] = len(ops)
-            if r.need_dx and r.pair is not None:
-                if id(r.pair) in pair_pending:      # second of the pair (in backward order): both dY are final now
-                    first, second = (r, r.pair) if r.pair_first else (r.pair, r)
-                    dst, acc = self._grad_target(r.x)
-                    if r.pw_b:
-                        ops.append(_op(L.OP_CONV_PW_BWD_DATA, p=[first.y, second.y, first.wb, dst],
-                                       i=[first.cout, second.cout, first.cout, first.ldwb, r.x.ld, r.x.B, r.x.H, r.x.W, r.cin, acc]))
-                    else:
-                        ops.append(_op(L.OP_CONV_BWD_DATA_PAIR, p=[first.y, second.y, first.wb, dst],
-                                       i=[first.cout, second.cout, first.cout, first.ldwb, r.x.ld, r.x.B, r.x.H, r.x.W, r.cin, acc]))
-                    writers.append((len(ops) - 1, r.x, r))
+            if not r.need_dx:
+                continue
+            if r.pair is not None and id(r.pair) not in pair_pending:
+                pair_pending.add(id(r))                             # first of the pair in backward order: wait for the sibling's dY
+                continue
+            dst, acc = self._grad_target(r.x)
+            kpad = [_rup8(r.cout)] if self.bf16 else []             # bf16 narrow kernels: K rows of the backward pack
+            if r.pair is not None:                                  # both siblings' dY are final now: one GEMM over K = c1 + c2
+                a, b = (r, r.pair) if r.pair_first else (r.pair, r)
+                if self.bf16:
+                    ops.append(_op(L.OP_BF16_CONV_BWD_DATA, p=[a.y, a.wb, dst, b.y],
+                                   i=[a.cout, a.ldwb, r.x.ldg, r.x.B, r.x.H, r.x.W, r.cin, a.cout + b.cout, 1, 1, acc, a.cout]))
                 else:
-                    pair_pending.add(id(r))
-            elif r.need_dx:
-                dst, acc = self._grad_target(r.x)
-                writers.append((len(ops), r.x, r))
-                if r.narrow_b and r.s == 2:
-                    ops.append(_op(L.OP_CONV_NARROW_DGRAD_S2, p=[dy, r.wb, dst],
-                                   i=[lddy, r.ldwb, r.x.ld, r.x.B, r.x.H, r.x.W, r.cin, r.cout, r.k, r.s, acc]))
-                elif r.narrow_b:     # x = dY (Cout channels), output = dX (Cin channels), backward pack, flipped taps
-                    ops.append(_op(L.OP_CONV_NARROW, p=[dy, r.wb, None, dst, None],
-                                   i=[lddy, r.ldwb, r.x.ld, r.x.B, r.x.H, r.x.W, r.cout, r.cin, 1, 1, acc]))
-                elif r.s2m_b:
-                    ops.append(_op(L.OP_CONV_BWD_DATA_S2M, p=[dy, r.wb, dst],
-                                   i=[lddy, r.ldwb, r.x.ld, r.x.B, r.x.H, r.x.W, r.cin, r.cout, r.k, r.s, acc]))
-                elif r.pw_b:
-                    ops.append(_op(L.OP_CONV_PW_BWD_DATA, p=[dy, None, r.wb, dst],
-                                   i=[r.cout, 0, lddy, r.ldwb, r.x.ld, r.x.B, r.x.H, r.x.W, r.cin, acc]))
-                elif r.wino_b:
-                    ops.append(_op(L.OP_CONV_WINO_BWD_DATA, p=[dy, r.wb, dst],
-                                   i=[lddy, r.ldwb, r.x.ld, r.x.B, r.x.H, r.x.W, r.cin, r.cout, acc]))
-                else:
-                    ops.append(_op(L.OP_CONV_BWD_DATA, p=[dy, r.wb, dst],
-                                   i=[lddy, r.ldwb, r.x.ld, r.x.B, r.x.H, r.x.W, r.cin, kcout, r.k, r.s, acc]))
+                    ops.append(_op(L.OP_CONV_PW_BWD_DATA if r.pw_b else L.OP_CONV_BWD_DATA_PAIR, p=[a.y, b.y, a.wb, dst],
+                                   i=[a.cout, b.cout, a.cout, a.ldwb, r.x.ld, r.x.B, r.x.H, r.x.W, r.cin, acc]))
+            elif r.narrow_b and r.s == 2:
+                ops.append(_op(K["narrow_s2"], p=[dy, r.wb, dst],
+                               i=[lddy, r.ldwb, r.x.ldg, r.x.B, r.x.H, r.x.W, r.cin, r.cout, r.k, r.s, acc] + kpad))
+            elif r.narrow_b:     # x = dY (Cout channels), output = dX (Cin channels), backward pack, flipped taps
+                ops.append(_op(K["narrow"], p=[dy, r.wb, None, dst, None],
+                               i=[lddy, r.ldwb, r.x.ldg, r.x.B, r.x.H, r.x.W, r.cout, r.cin, 1, 1, acc] + kpad))
+            elif r.s2m_b:
+                ops.append(_op(L.OP_CONV_BWD_DATA_S2M, p=[dy, r.wb, dst],
+                               i=[lddy, r.ldwb, r.x.ld, r.x.B, r.x.H, r.x.W, r.cin, r.cout, r.k, r.s, acc]))
+            elif r.pw_b:
+                ops.append(_op(L.OP_CONV_PW_BWD_DATA, p=[dy, None, r.wb, dst],
+                               i=[r.cout, 0, lddy, r.ldwb, r.x.ld, r.x.B, r.x.H, r.x.W, r.cin, acc]))
+            elif r.wino_b:
+                ops.append(_op(L.OP_CONV_WINO_BWD_DATA, p=[dy, r.wb, dst],
+                               i=[lddy, r.ldwb, r.x.ld, r.x.B, r.x.H, r.x.W, r.cin, r.cout, acc]))
+            else:
+                ops.append(_op(K["dgrad"], p=[dy, r.wb, dst],
+                               i=[lddy, r.ldwb, r.x.ldg, r.x.B, r.x.H, r.x.W, r.cin, kcout, r.k, r.s, acc]))
         # (folding the BatchNorm-backward sums into the epilogue of the backward-data GEMM that finishes a layer's gradient was
         # built, tested and measured in round 2: backward-data 5.74 -> 7.26 ms against 0.85 ms saved in the reduce pass; retired)
         return ops

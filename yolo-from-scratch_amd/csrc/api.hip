@@ -121,9 +121,15 @@ static int run_one(const yh_op &o, void *st) {
         case YH_OP_NOP:
             return 0;
         case YH_OP_CONV_NARROW:
-            if (p[10])
+            if (p[10]) {                    /* the prologue form has neither flipped taps nor accumulation: refuse, never drop them */
+                if (i[9] || i[10]) {
+                    yh_set_error("yh_run: a CONV_NARROW record with an input prologue table cannot set flip_taps (%d) or accumulate (%d)",
+                                 i[9], i[10]);
+                    return YH_E_BADARG;
+                }
                 return yh_conv_narrow_act((const float *)p[0], i[0], (const float *)p[10], i[17], (const float *)p[1], i[1], (const float *)p[2],
                                           (float *)p[3], i[2], (float *)p[4], i[3], i[4], i[5], i[6], i[7], i[8], st);
+            }
             return yh_conv_narrow((const float *)p[0], i[0], (const float *)p[1], i[1], (const float *)p[2], (float *)p[3], i[2],
                                   (float *)p[4], i[3], i[4], i[5], i[6], i[7], i[8], i[9], i[10], st);
         case YH_OP_CONV_NARROW_DGRAD_S2:    /* same argument slots as YH_OP_CONV_BWD_DATA */
